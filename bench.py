@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X batched field engine.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline only: it sets up the operands, warms up, times the K steps, writes the outputs when
+--dump-outputs is given and prints the line.  --full adds everything else this script measures or checks: the placement probe,
+the per-launch median pass, the other data sets, fields and curve legs, the fused chain, the time.c protocol on the GPU, the X25519
+and X448 ladders, the oracle check of the timed outputs, the rocprofv3 traffic passes and the CPU baseline (the --no-* options
+leave parts of it out).
+--dump-outputs DIR: after the timed steps, the limbs of the last step's modmul output for a fixed sample of elements
+(dump_outputs()), so that two builds can be compared output for output on identical inputs.
 
 Workload (BASELINE.json configs[1]): batched modmul modulo 2^255-19, 5 x 51-bit limbs, 2^24 field
 elements per GPU in limb-interleaved SoA, inputs resident in HBM before the timed region.  One step =
@@ -388,6 +396,27 @@ def contract_line(d, detail_note=DETAIL_NAME):
     return line
 
 
+DUMP_ELEMENTS = 1 << 20        # elements written by --dump-outputs over all ranks: 48 MB of float64 limbs and indices
+
+
+def dump_outputs(out_dir, F, c, n, rank, world):
+    """--dump-outputs: what a caller of the timed path receives from its last step, c = a * b, as limbs (non-canonical ones
+    included): DIR/modmul_X25519.npy (DIR/modmul_X25519_rank<r>.npy when there are several ranks), float64 [5, k], limb i of the t-th
+    sampled element; and DIR/modmul_X25519_index.npy, float64 [k], the element indices of the sample, ascending.  The limbs are below
+    2^53, so float64 holds them exactly.  The sample is the same in every run: all n elements when n <= DUMP_ELEMENTS / world,
+    otherwise the DUMP_ELEMENTS / world indices numpy's default_rng(0) draws without replacement."""
+    import numpy as np
+    import torch
+    k = min(n, DUMP_ELEMENTS // world)
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    limbs = F.to_flat(c)[:, torch.from_numpy(idx).to(c.device)].cpu().numpy().view(np.uint64)
+    assert int(limbs.max()) < 1 << 53, "a limb of the modmul output does not fit a float64 exactly"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "modmul_X25519%s.npy" % ("_rank%d" % rank if world > 1 else "")), limbs.astype(np.float64))
+    if rank == 0:
+        np.save(os.path.join(out_dir, "modmul_X25519_index.npy"), idx.astype(np.float64))
+
+
 def launch_ranks(n_ranks, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves, one process per GPU, through
     torch.distributed.run (the command the driver uses for N>1), relay their output and return their exit code.
@@ -419,7 +448,15 @@ def main():
                          "2^MA_BENCH_LOG2_LADDER_TOTAL (26) records divided over the N ranks.  The headline modmul line is weak either way.")
     ap.add_argument("--launch-check", action="store_true",
                     help="only check the rank launch: gloo group over the N ranks, no GPU work (tests/test_bench_launch.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every side measurement and check as well (see the module docstring); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed sample of the last step's modmul output to DIR/*.npy (float64 limbs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.no_ladder = args.no_cpu = args.no_others = args.no_traffic = args.no_verify = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -483,7 +520,8 @@ def main():
     # MA_BENCH_PLACEMENTS (default 4) operand triples with identical contents are allocated one after the other and each is
     # probed with 10 launches; all probe rates are reported.  The timed region runs on the FIRST-allocated triple -- what a
     # caller that allocates once gets -- unless MA_BENCH_KEEP_BEST=1 asks for the fastest of the probed ones (rounds 1-2).
-    placements = max(1, int(os.environ.get("MA_BENCH_PLACEMENTS", "4")))
+    # A plain run (no --full) probes nothing: it times the first-allocated triple, as the probe's default policy does.
+    placements = max(1, int(os.environ.get("MA_BENCH_PLACEMENTS", "4"))) if args.full else 1
     keep_best = os.environ.get("MA_BENCH_KEEP_BEST") == "1"
     probe_rates = []
     if placements > 1:
@@ -512,6 +550,22 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    def warm_clock(fn, warm=3, warm_ms=60.0):
+        # >= `warm` launches AND >= 60 ms of them (at most 2000): the first 20-40 streaming launches after a host-side pause run 2-5 %
+        # slower while the part brings its clocks back (profiles/history/r04_chain_dvfs.log: every kernel, not one in particular)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(warm):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        spent = e0.elapsed_time(e1)
+        for _ in range(min(2000, int(max(0.0, warm_ms - spent) / max(spent / warm, 1e-3)))):
+            fn()
+        torch.cuda.synchronize()
+
+    # the set-up leaves the part idle: its clocks are brought back before the W counted warm-up steps
+    warm_clock(lambda: F.modmul(a, b, out=c))
     for _ in range(args.warmup):
         F.modmul(a, b, out=c)
     barrier()
@@ -529,43 +583,38 @@ def main():
         dt, kern_ms = max_over_ranks([dt, kern_ms])
     value = world * n * args.steps / dt
     achieved = BYTES_PER_MODMUL * n / (kern_ms * 1e-3) / 1e9
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, F, c, n, rank, world)
 
-    # SURVEY 8(d) "report median": per-launch durations of a SEPARATE pass of the same launches on the same buffers (one event
-    # between consecutive launches; the timed region above keeps the contract's single bracket and is not touched)
-    nl = max(20, min(args.steps, 100))
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(nl + 1)]
-    torch.cuda.synchronize()
-    for i in range(nl):
-        evs[i].record()
-        F.modmul(a, b, out=c)
-    evs[nl].record()
-    torch.cuda.synchronize()
-    per_launch = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(nl))
-    launch_stats = {"launches": nl, "median_ms": per_launch[nl // 2] if nl % 2 else 0.5 * (per_launch[nl // 2 - 1] + per_launch[nl // 2]),
-                    "min_ms": per_launch[0], "max_ms": per_launch[-1], "p10_ms": per_launch[nl // 10], "p90_ms": per_launch[(9 * nl) // 10]}
-    launch_stats["median_GBps"] = BYTES_PER_MODMUL * n / (launch_stats["median_ms"] * 1e-3) / 1e9
-    launch_stats["frac_of_hbm_peak_median"] = launch_stats["median_GBps"] / HBM_PEAK_GBS
+    launch_stats = None
+    if args.full:
+        # SURVEY 8(d) "report median": per-launch durations of a SEPARATE pass of the same launches on the same buffers (one event
+        # between consecutive launches; the timed region above keeps the contract's single bracket and is not touched)
+        nl = max(20, min(args.steps, 100))
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(nl + 1)]
+        torch.cuda.synchronize()
+        for i in range(nl):
+            evs[i].record()
+            F.modmul(a, b, out=c)
+        evs[nl].record()
+        torch.cuda.synchronize()
+        per_launch = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(nl))
+        launch_stats = {"launches": nl, "median_ms": per_launch[nl // 2] if nl % 2 else 0.5 * (per_launch[nl // 2 - 1] + per_launch[nl // 2]),
+                        "min_ms": per_launch[0], "max_ms": per_launch[-1], "p10_ms": per_launch[nl // 10], "p90_ms": per_launch[(9 * nl) // 10]}
+        launch_stats["median_GBps"] = BYTES_PER_MODMUL * n / (launch_stats["median_ms"] * 1e-3) / 1e9
+        launch_stats["frac_of_hbm_peak_median"] = launch_stats["median_GBps"] / HBM_PEAK_GBS
 
-    # size-independent correctness guard inside the bench: a*b == b*a and (a*b) canonical form is stable
-    chk = F.modmul(b, a)
-    assert torch.equal(chk, c), "modmul is not commutative bit-for-bit: kernel bug"
-    del chk
+        # size-independent correctness guard inside the bench: a*b == b*a and (a*b) canonical form is stable
+        chk = F.modmul(b, a)
+        assert torch.equal(chk, c), "modmul is not commutative bit-for-bit: kernel bug"
+        del chk
 
     def rate(fn, reps=20, warm=3, warm_ms=60.0):
         # >= 3 warm-up launches AND >= 60 ms of them: the side legs are separated by host work (allocations, input
-        # generation, a plug-in load), during which the part drops its clocks; the first 20-40 streaming launches after such a gap
-        # run 2-5 % slower while they ramp back (profiles/history/r04_chain_dvfs.log: every kernel, not one in
-        # particular), and three launches of 0.3 ms do not cover that.  Kernels of tens of ms per launch get their three.
+        # generation, a plug-in load), during which the part drops its clocks, and three launches of 0.3 ms do not cover the
+        # ramp back (warm_clock).  Kernels of tens of ms per launch get their three.
+        warm_clock(fn, warm, warm_ms)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(warm):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        spent = e0.elapsed_time(e1)
-        for _ in range(min(2000, int(max(0.0, warm_ms - spent) / max(spent / warm, 1e-3)))):
-            fn()
-        torch.cuda.synchronize()
         e0.record()
         for _ in range(reps):
             fn()
@@ -1057,7 +1106,8 @@ def main():
             "x25519": ladder,
             "x448": x448,
             # per-launch durations of a separate pass of the same launches (SURVEY 8(d) "report median"); ms_per_step above is the contract's mean
-            "ms_per_step_median": launch_stats["median_ms"], "ms_per_step_min": launch_stats["min_ms"], "ms_per_step_max": launch_stats["max_ms"],
+            "ms_per_step_median": (launch_stats or {}).get("median_ms"), "ms_per_step_min": (launch_stats or {}).get("min_ms"),
+            "ms_per_step_max": (launch_stats or {}).get("max_ms"),
             "launch_stats": launch_stats,
             "data_sets": data_sets,
             "other_configs": others,
@@ -1066,6 +1116,7 @@ def main():
             "rank_spread": {"modmul_per_s": {"min": min(per_rank), "mean": sum(per_rank) / len(per_rank), "max": max(per_rank)},
                             "kernel_ms": {"min": min(kms), "mean": sum(kms) / len(kms), "max": max(kms)}},
             "dist": dist_info,
+            "full": args.full,
         }
         # Everything measured goes to the detail file beside this script (MA_BENCH_DETAIL names another path) and to stdout lines that
         # start with "# "; the LAST stdout line is the compact contract line (<= LINE_LIMIT bytes), the only line that starts with "{".

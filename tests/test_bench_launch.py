@@ -33,3 +33,12 @@ def test_self_launch_propagates_failure():
     p = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-others", "--no-ladder"])
     assert p.returncode != 0
     assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
+
+
+def test_options_and_refused_step_counts():
+    # --full and --dump-outputs exist; a step count that cannot give ms_per_step is refused before any GPU work
+    p = _bench(["--help"])
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        p = _bench(bad)
+        assert p.returncode == 2 and "--steps must be at least 1" in p.stderr, p.stderr[-500:]

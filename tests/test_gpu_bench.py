@@ -43,9 +43,9 @@ def _run(args, env_extra, tmp_path):
 
 
 def test_bench_driver_command_exactly(tmp_path):
-    """the command the driver runs at round end, no flag removed: `python bench.py --gpus 1 --steps 20 --warmup 5` -- every side leg, the CPU
-    baseline and the rocprofv3 child passes included.  What the driver needs is in the <= 4 KB line; everything is in the detail file."""
-    d, full = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], {}, tmp_path, timeout=1500)
+    """the full benchmark, no other flag: `python bench.py --full --gpus 1 --steps 20 --warmup 5` -- every side leg, the CPU baseline and
+    the rocprofv3 child passes included.  The headline and its summaries are in the <= 4 KB line; everything is in the detail file."""
+    d, full = _bench(["--full", "--gpus", "1", "--steps", "20", "--warmup", "5"], {}, tmp_path, timeout=1500)
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["scaling"] == "weak" and d["vs_baseline"] is None
     r, c, x = d["roofline"], d["cpu_baseline"], d["x25519"]
     assert r["bound"] == "hbm" and 0.3 < r["frac"] < 1.0 and 0.99 < r["traffic"] / r["algorithmic_bytes_per_launch"] < 1.05
@@ -64,8 +64,45 @@ def test_bench_driver_command_exactly(tmp_path):
         assert rl["mad_per_scalar"] >= 0.98 * rl["mad_floor_per_scalar"], k
 
 
+def test_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path, oracle):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the headline alone (no probe, no side leg, no check, no child
+    pass), K timed steps; with --dump-outputs DIR the last step's modmul output for bench.dump_outputs' fixed sample, equal to the
+    oracle's products of the same inputs (tests/util.py's model of the device recipe) and identical from run to run."""
+    import numpy as np
+    from tests.util import oracle_bin, uniform_model, uniform_soa
+    p = (1 << 255) - 19
+
+    def plain(log2_elems, out):
+        line, d = _bench(["--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(out)], {"MA_BENCH_LOG2_ELEMS": str(log2_elems)}, tmp_path)
+        assert line["steps"] == 7 and line["warmup"] == 2 and line["n_gpus"] == 1 and line["ms_per_step"] > 0
+        assert line["metric"] == "256-bit modmul/s (2^255-19)" and line["unit"] == "modmul/s" and line["higher_is_better"] is True and line["dtype"] == "u64"
+        assert abs(line["value"] - (1 << log2_elems) / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+        assert line["cpu_baseline"] is None and line["x25519"] is None and line["verified_against_oracle"] is None
+        assert d["full"] is False and d["config"]["placement_probe_GBps"] == [] and d["launch_stats"] is None and d["other_configs"] == {}
+        assert sorted(os.listdir(out)) == ["modmul_X25519.npy", "modmul_X25519_index.npy"]
+        assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 << 20
+        c, idx = np.load(out / "modmul_X25519.npy"), np.load(out / "modmul_X25519_index.npy")
+        assert c.dtype == idx.dtype == np.float64 and c.shape == (5, idx.size)
+        return c, idx
+
+    c, idx = plain(16, tmp_path / "small0")                        # every element of a 2^16 batch
+    assert np.array_equal(idx, np.arange(1 << 16))
+    a, b = uniform_soa("X25519", 1 << 16, 42, 0), uniform_soa("X25519", 1 << 16, 42, 1)
+    assert np.array_equal(c.astype(np.uint64), oracle_bin(oracle, "modmul", "X25519", a, b))
+    c2, idx2 = plain(16, tmp_path / "small1")
+    assert np.array_equal(c, c2) and np.array_equal(idx, idx2)
+    c, idx = plain(24, tmp_path / "full_size")                     # the benchmark's own size: a sample of 2^20 of the 2^24 elements
+    assert c.shape == (5, 1 << 20) and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 1 << 24
+    j = idx[::4096].astype(np.int64)
+
+    def limbs(array):
+        v = [uniform_model(p, 255, 42, array, int(t)) for t in j]
+        return np.array([[(x >> (51 * i)) & ((1 << 51) - 1) for x in v] for i in range(4)] + [[x >> 204 for x in v]], dtype=np.uint64)
+    assert np.array_equal(c[:, ::4096].astype(np.uint64), oracle_bin(oracle, "modmul", "X25519", limbs(0), limbs(1)))
+
+
 def test_bench_line_contract(tmp_path):
-    d = _run(["--steps", "20", "--warmup", "5", "--no-cpu", "--no-others"], {}, tmp_path)
+    d = _run(["--full", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-others"], {}, tmp_path)
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["scaling"] == "weak" and d["vs_baseline"] is None
     assert d["dtype"] == "u64" and d["data"] == "synthetic" and "workload" in d["config"] and "model" not in d["config"]
     r = d["roofline"]
@@ -83,7 +120,7 @@ def test_bench_line_contract(tmp_path):
 
 
 def test_bench_rccl_path_one_rank(tmp_path):
-    d = _run(["--steps", "10", "--warmup", "3", "--no-cpu", "--no-others", "--no-traffic"], {"MA_BENCH_FORCE_DIST": "1", "MASTER_PORT": "29533"}, tmp_path)
+    d = _run(["--full", "--steps", "10", "--warmup", "3", "--no-cpu", "--no-others", "--no-traffic"], {"MA_BENCH_FORCE_DIST": "1", "MASTER_PORT": "29533"}, tmp_path)
     assert d["n_gpus"] == 1 and d["x25519"]["gather_ms"] is not None and d["x25519"]["gather_ms"] > 0
 
 
@@ -92,7 +129,7 @@ def test_bench_self_launch_two_ranks_gloo(tmp_path):
     this box; gloo carries the collectives) and relays rank 0's single line."""
     # --scaling strong: BASELINE configs[4] literally -- 2^MA_BENCH_LOG2_LADDER_TOTAL records divided over the ranks in contiguous shards
     # (here 2^19 over two) and gathered to rank 0
-    line, d = _bench(["--gpus", "2", "--steps", "10", "--warmup", "3", "--no-cpu", "--no-others", "--scaling", "strong"],
+    line, d = _bench(["--full", "--gpus", "2", "--steps", "10", "--warmup", "3", "--no-cpu", "--no-others", "--scaling", "strong"],
                      dict(MA_BENCH_BACKEND="gloo", MA_BENCH_LOG2_ELEMS="22", MA_BENCH_LOG2_LADDER_TOTAL="19"), tmp_path, clean_env=True)
     assert line["n_gpus"] == 2 and line["x25519"]["scalars_total"] == 1 << 19 and line["x25519"]["gather_ms"] > 0 and line["verified_against_oracle"]["ranks_checked"] == 2
     assert line["dist"] == {"backend": "gloo", "world_size": 2, "distinct_devices": 1} and len(line["rank_spread_modmul_per_s"]) == 3
@@ -122,7 +159,7 @@ def test_bench_eight_ranks_on_one_gpu_equal_one_rank(tmp_path):
     contiguous shards (simd/README.md:4-16: independent units, no exchange step), every rank verifies its own shard against the oracle,
     rank 0 gathers all results; their digest must equal the digest of a ONE-rank run over the same 2^16 records."""
     def run(n):
-        line, full = _bench(["--gpus", str(n), "--steps", "5", "--warmup", "2", "--no-cpu", "--no-others", "--no-traffic", "--scaling", "strong"],
+        line, full = _bench(["--full", "--gpus", str(n), "--steps", "5", "--warmup", "2", "--no-cpu", "--no-others", "--no-traffic", "--scaling", "strong"],
                             dict(MA_BENCH_BACKEND="gloo", MA_BENCH_LOG2_ELEMS="18", MA_BENCH_LOG2_LADDER_TOTAL="16", MA_BENCH_PLACEMENTS="1"), tmp_path, timeout=1500, clean_env=True)
         # the compact line alone carries what a SCALE record needs at every N
         assert line["n_gpus"] == n and line["verified_against_oracle"]["ranks_checked"] == n and line["x25519"]["records_sha256"] == full["x25519"]["records_sha256"]

@@ -153,7 +153,7 @@ def test_bench_strong_scaling_switch_and_new_keys(tmp_path):
     driver parses is the compact one, tests/test_gpu_bench.py)."""
     detail = str(tmp_path / "detail.json")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MA_BENCH_LOG2_LADDER_TOTAL="20", MA_BENCH_LOG2_ELEMS="22", MA_BENCH_LOG2_X448="16", MA_BENCH_DETAIL=detail)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--no-cpu", "--no-others", "--no-traffic", "--scaling", "strong"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "3", "--no-cpu", "--no-others", "--no-traffic", "--scaling", "strong"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

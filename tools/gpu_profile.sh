@@ -15,12 +15,12 @@ cd /tmp && export TMPDIR=/tmp
 export MA_BENCH_PLACEMENTS=1
 # (--no-others: the side figures launch the same kernel symbol on other data sets and on the other HBM layout; without them the
 # per-kernel average of --stats covers the headline launches only)
-MA_BENCH_DETAIL=$OUT/bench_under_rocprof_detail.json timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $PY $R/bench.py --steps 100 --warmup 10 --no-cpu --no-others --no-traffic > $OUT/bench_under_rocprof.log 2>&1
-MA_BENCH_DETAIL=$OUT/pmc_detail.json timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- $PY $R/bench.py --steps 5 --warmup 2 --no-cpu --no-ladder --no-others --no-traffic > $OUT/pmc_fetch.log 2>&1
-MA_BENCH_DETAIL=$OUT/pmc_detail.json timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- $PY $R/bench.py --steps 5 --warmup 2 --no-cpu --no-ladder --no-others --no-traffic > $OUT/pmc_write.log 2>&1
+MA_BENCH_DETAIL=$OUT/bench_under_rocprof_detail.json timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $PY $R/bench.py --full --steps 100 --warmup 10 --no-cpu --no-others --no-traffic > $OUT/bench_under_rocprof.log 2>&1
+MA_BENCH_DETAIL=$OUT/pmc_detail.json timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -- $PY $R/bench.py --full --steps 5 --warmup 2 --no-cpu --no-ladder --no-others --no-traffic > $OUT/pmc_fetch.log 2>&1
+MA_BENCH_DETAIL=$OUT/pmc_detail.json timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -- $PY $R/bench.py --full --steps 5 --warmup 2 --no-cpu --no-ladder --no-others --no-traffic > $OUT/pmc_write.log 2>&1
 cd $R
 unset MA_BENCH_PLACEMENTS
-# the driver's command, as the driver runs it; the detail file beside bench.py is copied next to the log
-timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 < /dev/null > $OUT/bench_plain.log 2>&1
+# the full benchmark at the standard step counts; the detail file beside bench.py is copied next to the log
+timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 < /dev/null > $OUT/bench_plain.log 2>&1
 cp $R/bench_detail.json $OUT/bench_plain_detail.json
 tail -1 $OUT/bench_plain.log | cut -c1-600
