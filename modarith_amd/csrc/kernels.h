@@ -286,9 +286,17 @@ __global__ __launch_bounds__(BLOCK) void k_nsqr(spint* a, int k, size_t n, Ld ld
     for (size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x; t < n; t += (size_t)gridDim.x * BLOCK) {
         spint x[1][P::N];
         load_soa<P, 1>(a, ld, t, x);
-        bool fast = false;
-        if constexpr (P::SPLIT > 0) fast = __all(in_split_contract<P>(x[0]));
-        if (fast) Field<P, true>::modnsqr(x[0], k); else Field<P, false>::modnsqr(x[0], k);
+        // the vote is taken before EVERY squaring, not once on the input: the limb contract is not closed under squaring for every input
+        // inside it.  A Montgomery product leaves its top limb unmasked, below (v(a)^2 / R + p) >> Radix (Nlimbs - 1); with 2^(Radix+2) - 1
+        // in every limb the value is 4 * 2^(Radix Nlimbs) and the square's top limb reaches 2^(Radix+4) -- outside the contract of the
+        // split products, which then returned other words than the reference from the second squaring on (tests/test_gpu_edge_products.py;
+        // NIST256, k = 5, a = [1fffffffffffff x 5]: limb 4 = 55e30b312da0744, reference c660b78c46b68bd4)
+#pragma unroll 1
+        for (int i = 0; i < k; i++) {
+            bool fast = false;
+            if constexpr (P::SPLIT > 0) fast = __all(in_split_contract<P>(x[0]));
+            if (fast) Field<P, true>::modsqr(x[0], x[0]); else Field<P, false>::modsqr(x[0], x[0]);
+        }
         store_soa<P, 1>(a, ld, t, x);
     }
 }

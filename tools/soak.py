@@ -2,8 +2,12 @@
 """Soak runs on the GPU box (not part of the pytest suites: minutes, not seconds).
 
   soak.py field   exact vs split/chain products on 2^22 elements per prime whose limbs are drawn from the contract's
-                  edge classes (0, 1, 2^R-1, 2^R, 2^(R+1)-1, 2^(R+2)-1, random), plus 48-operation chains from
-                  in-range values: the product policies must agree bit for bit (checksums compared across three child processes: MA_FORCE_EXACT=1, MA_FORCE_FAST=1, default)
+                  edge classes (0, 1, 2^R-1, 2^R, 2^(R+1)-1, 2^(R+2)-1, random) -- the same class in every limb of both operands
+                  first -- plus 48-operation chains from in-range values: the product policies must agree LIMB FOR LIMB (three child
+                  processes, MA_FORCE_EXACT=1, MA_FORCE_FAST=1, default; each saves its result tensors, the forced-fast and default
+                  ones are compared with the exact child's by torch.equal).  The suite covers the budget's edge against the ORACLE,
+                  for every prime, on 2^14 + 3 elements and under the three policies (tests/test_gpu_edge_products.py; host build of
+                  the same arithmetic: tests/test_fast_products_host.py); this soak adds volume, not a reference.
   soak.py curves  2^13 .. 2^16 random scalars x random points for each of the eleven curves, fused ecn mul on the GPU against the CPU oracle,
                   projective limbs compared
   soak.py mul2    2^10 .. 2^12 (scalar pair, point pair) records per curve through Curve.mul2(exact=True) against the oracle's mul2, projective limbs
@@ -16,17 +20,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def field_child(out):
-    import json, torch
+def field_child(out, only):
+    import torch
     from modarith_amd.field import Field
     from modarith_amd.params import derive
     from modarith_amd import emit
     res = {}
     n = 1 << 22
-    for name in emit.BUILT_PRIMES:
+    for name in [only]:
         fp = derive(name)
-        if emit.split_point(fp) == 0:
-            continue
         F = Field(name, tile=None)          # flat rows, as the [N, n] indexing below assumes
         R = fp.radix
         g = torch.Generator(device="cuda").manual_seed(1234)
@@ -36,6 +38,11 @@ def field_child(out):
             rnd = torch.randint(0, 1 << R, (fp.nlimbs, n), dtype=torch.int64, device="cuda", generator=g)
             return torch.where(cls < 7, edges[cls.clamp(max=6)], rnd)
         a, b = draw(), draw()
+        # the same class in every limb, every pair of classes: the all-maximal operands the overflow proofs of emit.split_point /
+        # chain_ok are about never come out of independent draws (nine limbs: one element in 10^18)
+        ne = edges.numel()
+        a[:, :ne * ne] = edges.repeat_interleave(ne)[None, :]
+        b[:, :ne * ne] = edges.repeat(ne)[None, :]
         outs = [F.modmul(a, b), F.modsqr(a), F.modmul(b, b)]
         if fp.montgomery:
             outs += [F.nres(a), F.redc(a)]
@@ -49,33 +56,41 @@ def field_child(out):
         for _ in range(16):
             c = F.modmul(c, y); c = F.modsqr(c); y = F.modadd(c, x)
         outs.append(c)
-        res[name] = [[int(o.sum().item()) & (2**64 - 1), int(o.flatten().cumsum(0)[-1].item()) & (2**64 - 1),
-                      int((o ^ (o >> 17)).sum().item()) & (2**64 - 1)] for o in outs]
-    json.dump(res, open(out, "w"))
+        res[name] = [o.cpu() for o in outs]
+    torch.save(res, out)
 
 
 def field():
     """three child processes, one per product policy (the switches are process-static): MA_FORCE_EXACT=1 (128-bit
     products: the reference arithmetic), MA_FORCE_FAST=1 (split / chain products, unguarded) and the default per-wave
     vote.  All edge classes are inside the split contract, so the default leg takes the split path too; the exact
-    leg is the one that differs in code.  (Against the CPU oracle: tests/test_gpu_round2.py, three primes.)"""
-    import json
+    leg is the one that differs in code.  (Against the CPU oracle, every prime: tests/test_gpu_edge_products.py.)"""
+    import tempfile, torch
     legs = (("exact", {"MA_FORCE_EXACT": "1"}), ("fast", {"MA_FORCE_FAST": "1"}), ("default", {}))
-    outs = []
-    for tag, extra in legs:
-        f = "/tmp/soak_field_%s.json" % tag
-        env = {k: v for k, v in os.environ.items() if k not in ("MA_FORCE_EXACT", "MA_FORCE_FAST")}
-        env.update(extra)
-        subprocess.run([sys.executable, __file__, "field-child", f], env=env, check=True)
-        outs.append(json.load(open(f)))
-    names = ["modmul(a,b)", "modsqr(a)", "modmul(b,b)", "nres(a)|chain", "redc(a)", "chain"]
+    names = ["modmul(a,b)", "modsqr(a)", "modmul(b,b)", "nres(a)", "redc(a)", "chain"]
     bad = []
-    for k in outs[0]:
-        for leg, o in zip(legs[1:], outs[1:]):
-            if outs[0][k] != o[k]:
-                bad.append((k, leg[0]))
-                print(k, leg[0], "differs from exact in:", [names[i] if len(o[k]) == 6 or i < 3 else "chain" for i in range(len(o[k])) if outs[0][k][i] != o[k][i]])
-    print("field soak: %d primes, 2^22 edge-class elements each, exact == split/chain == default: %s" % (len(outs[0]), "ALL EQUAL" if not bad else "MISMATCH " + str(bad)))
+    from modarith_amd import emit
+    from modarith_amd.params import derive
+    primes = [name for name in emit.BUILT_PRIMES if emit.split_point(derive(name)) > 0]
+    with tempfile.TemporaryDirectory() as d:
+        for k in primes:                                 # one prime at a time: a leg's tensors are up to 2.5 GB
+            exact = None
+            for tag, extra in legs:
+                f = os.path.join(d, "soak_field_%s.pt" % tag)
+                env = {k_: v for k_, v in os.environ.items() if k_ not in ("MA_FORCE_EXACT", "MA_FORCE_FAST")}
+                env.update(extra)
+                subprocess.run([sys.executable, __file__, "field-child", f, k], env=env, check=True)
+                o = torch.load(f)[k]
+                os.remove(f)
+                if exact is None:
+                    exact = o
+                    continue
+                label = names if len(exact) == 6 else names[:3] + ["chain"]
+                diff = [label[i] for i in range(len(exact)) if not torch.equal(exact[i], o[i])]
+                if diff:
+                    bad.append((k, tag))
+                    print(k, tag, "differs from exact in:", diff, flush=True)
+    print("field soak: %d primes, 2^22 edge-class elements each, exact == split/chain == default, limb for limb: %s" % (len(primes), "ALL EQUAL" if not bad else "MISMATCH " + str(bad)))
     return 1 if bad else 0
 
 
@@ -189,7 +204,7 @@ def fused():
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "field"
     if mode == "field-child":
-        field_child(sys.argv[2])
+        field_child(sys.argv[2], sys.argv[3])
     elif mode == "field":
         sys.exit(field())
     elif mode == "mul2":
