@@ -19,7 +19,9 @@
 #include <string.h>
 
 /* ------------------------------------------- "paste field.c here" ------------------------------------------- */
-#ifdef USE_X448
+#if defined(FIELD_HEADER)          /* another pasted field: -DFIELD_HEADER='"field_X25519_w32.h"' (the 32-bit word form) */
+#include FIELD_HEADER
+#elif defined(USE_X448)
 #include "field_X448.h"
 #else
 #include "field_X25519.h"

@@ -88,6 +88,14 @@ UTIL_FUNCS = ("modarith_amd_abi_version", "modarith_amd_last_error", "modarith_a
               "modarith_amd_field_info", "modarith_amd_recommended_ld", "modarith_amd_recommended_ld_for", "modarith_amd_batch_words", "modarith_amd_scratch_trim",
               "modarith_amd_last_launch", "modarith_amd_status", "modarith_amd_clear_status", "modarith_amd_thread_status", "modarith_amd_clear_thread_status", "modarith_amd_sclk_probe", "modarith_amd_wall_clock_khz")
 
+# ---- the 32-bit word form (include/modarith_amd_w32.h): tables of its own -- <fn>_<P>_w32_batch / <fn>_<P>_w32_ct
+W32_PRIMES = ("X25519", "NIST256", "X448")
+W32_ABSENT = ("modmuls", "modadd_lazy", "modsub_lazy", "modneg_lazy", "time_protocol")      # not offered at this word length
+_SIG_W32 = {fn: args for fn, args in _SIG.items() if fn not in W32_ABSENT}                   # same argument order, uint32_t limbs
+W32_BATCH_FUNCS = tuple(_SIG_W32)
+W32_SCALAR_FUNCS = SCALAR_FUNCS
+W32_UTIL_FUNCS = ("modarith_amd_w32_field_info", "modarith_amd_w32_aos_to_soa", "modarith_amd_w32_soa_to_aos", "modarith_amd_w32_batch_words")
+
 
 def _declare_curve(lib, C: str) -> None:
     """argtypes / restypes of the batched curve entry points ecn_<C>_*_batch of `lib` (the main library or a curve plug-in)"""
@@ -131,6 +139,16 @@ def load() -> ctypes.CDLL:
             f = getattr(lib, "%s_%s_batch" % (fn, P))
             f.argtypes = args
             f.restype = c_int
+    for P in W32_PRIMES:
+        for fn, args in _SIG_W32.items():
+            f = getattr(lib, "%s_%s_w32_batch" % (fn, P))
+            f.argtypes = args
+            f.restype = c_int
+    lib.modarith_amd_w32_aos_to_soa.argtypes = [_P, _P, c_size_t, c_int, c_size_t, _P]
+    lib.modarith_amd_w32_soa_to_aos.argtypes = [_P, _P, c_size_t, c_int, c_size_t, _P]
+    lib.modarith_amd_w32_field_info.argtypes = [c_char_p] + [ctypes.POINTER(c_int)] * 5
+    lib.modarith_amd_w32_batch_words.argtypes = [c_size_t, c_int, c_size_t]
+    lib.modarith_amd_w32_batch_words.restype = c_size_t
     for C in LADDERS:
         f = getattr(lib, "rfc7748_%s_batch" % C)
         f.argtypes = [_P, _P, _P, c_size_t, _P]

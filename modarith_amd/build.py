@@ -2,7 +2,7 @@
 
   python -m modarith_amd.build [--force]
 
-Steps: (1) the parameter driver emits csrc/generated/params_<PRIME>.h (modarith_amd.emit),
+Steps: (1) the parameter driver emits csrc/generated/params_<PRIME>.h and, for the 32-bit word form, w32_<PRIME>.h (modarith_amd.emit),
 (2) hipcc compiles one translation unit per prime plus the common one, in parallel,
 (3) hipcc links modarith_amd/libmodarith_amd.so.  hipcc cross-compiles without a GPU.
 """
@@ -32,7 +32,9 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-
 _CURVE_UNITS = ["capi_%s" % c for c in emit.BUILT_CURVES] + ["capi_%sW" % c for c in emit.BUILT_WCURVES]
 UNITS = ([(u, u, []) for u in ["capi_common", "capi_ED25519F", "capi_ED25519F2", "capi_ED448F", "capi_ED448F2", "capi_NIST256F", "capi_NIST256F2", "capi_SECP256K1F", "capi_SECP256K1F2", "capi_NIST256G", "capi_SECP256K1G", "capi_ED25519G", "capi_ED448G"] + ["capi_%s" % p for p in emit.CORE_PRIMES]]
          + [(u, "%s_part%d" % (u, part), ["-DMA_CURVE_PART=%d" % part]) for u in _CURVE_UNITS for part in (1, 2, 3)]
-         + [("generated/capi_%s" % p, "capi_%s" % p, []) for p in emit.EXTRA_PRIMES])
+         + [("generated/capi_%s" % p, "capi_%s" % p, []) for p in emit.EXTRA_PRIMES]
+         # the 32-bit word form (include/modarith_amd_w32.h): one unit per prime over capi_w32.inc, and the entry points of no single prime
+         + [("capi_%s_w32" % p, "capi_%s_w32" % p, []) for p in emit.W32_PRIMES] + [("capi_w32_common", "capi_w32_common", [])])
 # longest first, so the pool does not finish on a long tail: measured compile seconds of the slow units (8 jobs on 8 cores; the
 # rest take 10-30 s each)
 _COST = {"capi_SIDH751": 180, "capi_NIST521W_part2": 170, "capi_ED500_part2": 143, "capi_SIDH610": 105, "capi_NIST521W_part1": 91, "capi_CSIDH512": 90,
@@ -47,7 +49,8 @@ def _stamp() -> str:
         for f in sorted(files):
             h.update(f.encode())
             h.update(open(os.path.join(root, f), "rb").read())
-    h.update(open(os.path.join(os.path.dirname(HERE), "include", "modarith_amd.h"), "rb").read())
+    for header in ("modarith_amd.h", "modarith_amd_w32.h"):
+        h.update(open(os.path.join(os.path.dirname(HERE), "include", header), "rb").read())
     h.update(" ".join(FLAGS).encode())
     return h.hexdigest()
 

@@ -16,11 +16,37 @@
 #include <stdint.h>
 #include <type_traits>
 
-namespace ma {
+// Word length (the first argument of the reference generators).  64, the default: spint = u64, dpint = u128, namespace ma -- every
+// 64-bit translation unit sees exactly the text it saw before this switch existed.  32 (MA_WL defined to 32 before the first include;
+// csrc/kernels32.h, capi_w32.inc): spint = u32, dpint = u64, the form `pseudo.py 32` / `monty.py 32` emit -- every partial product is
+// one v_mad_u64_u32 into a 64-bit column, which IS the reference's dpint arithmetic, so only the exact product policy exists there
+// (P::SPLIT = 0: the FAST_ forms below are never instantiated).  The 32-bit form lives in a namespace of its own (ma32): a
+// translation unit holds one word length, and the two never share a template instantiation.
+#ifndef MA_WL
+#define MA_WL 64
+#endif
+#if MA_WL == 32
+#define MA_NS ma32
+#elif MA_WL == 64
+#define MA_NS ma
+#else
+#error "MA_WL must be 64 or 32"
+#endif
 
+namespace MA_NS {
+
+#if MA_WL == 32
+using spint = uint32_t;
+using sspint = int32_t;
+using dpint = uint64_t;
+using sdpint = int64_t;
+#else
 using spint = uint64_t;
 using sspint = int64_t;
 using dpint = unsigned __int128;
+using sdpint = __int128;
+#endif
+using word_t = uint64_t;     // byte records travel as 64-bit words at either word length (limbs_from_words / words_from_limbs)
 
 #ifndef MA_DEV          // tools/fe_host_check.hip defines it __host__ __device__ to run the same arithmetic on the CPU
 #define MA_DEV __device__ __forceinline__
@@ -185,7 +211,7 @@ struct Field {
             carry >>= RADIX;
         });
         n[N - 1] += (spint)carry;
-        return (spint)0 - ((n[N - 1] >> 1) >> 62);
+        return (spint)0 - ((n[N - 1] >> 1) >> (MA_WL - 2));
     }
 
     // n += x*p under an AND selector (caddp/addp: pseudo.py:202-213, monty.py:301-332)
@@ -805,7 +831,7 @@ struct Field {
     static MA_DEV void pm_modmli(const spint* a, int b, spint* c) {
         dpint t = 0;
         spint v[N];
-        const dpint bw = (dpint)(__int128)b;
+        const dpint bw = (dpint)(sdpint)b;
         static_for<0, N>([&](auto I) {
             t += (dpint)a[I] * bw;
             v[I] = (spint)t & MASK;
@@ -1185,7 +1211,7 @@ struct Field {
 
     // monty.py:876-978: trinomial fold, else Barrett-Dhem
     static MA_DEV void monty_modmli(const spint* a, int b, spint* c) {
-        const dpint bw = (dpint)(__int128)b;
+        const dpint bw = (dpint)(sdpint)b;
         dpint t = 0;
         if constexpr (P::TRIN > 0) {
             static_for<0, N>([&](auto I) {
@@ -1209,7 +1235,7 @@ struct Field {
             t += (dpint)a[N - 1] * bw;
             c[N - 1] = (spint)t;
             spint h = (spint)(t >> P::BARRETT_SHIFT);
-            spint q = (spint)(((dpint)h * (dpint)(spint)P::BARRETT_R) >> 64);
+            spint q = (spint)(((dpint)h * (dpint)(spint)P::BARRETT_R) >> MA_WL);
             bool propc = P::ppw(0) > 0;
             static_for<0, N>([&](auto I) {
                 constexpr int i = I;
@@ -1519,40 +1545,40 @@ struct Field {
     // turn big-endian (modimp/modexp) or little-endian (rfc7748) byte records into such words.
     static constexpr int NW = (P::NBYTES + 7) / 8;   // a short top word is zero-extended
 
-    static MA_DEV void limbs_from_words(const spint* w, spint* a) {
+    static MA_DEV void limbs_from_words(const word_t* w, spint* a) {
         static_for<0, N>([&](auto I) {
             constexpr int i = I;
             constexpr int o = RADIX * i, wi = o / 64, sh = o % 64;
-            spint val = 0;
+            word_t val = 0;
             if constexpr (wi < NW) {
                 val = w[wi] >> sh;
                 if constexpr (sh + RADIX > 64 && wi + 1 < NW) val |= w[wi + 1] << (64 - sh);
             }
             if constexpr (i < N - 1) val &= MASK;
-            a[i] = val;
+            a[i] = (spint)val;
         });
     }
     // limbs must be canonical (< 2^RADIX each), as redc leaves them
-    static MA_DEV void words_from_limbs(const spint* c, spint* w) {
+    static MA_DEV void words_from_limbs(const spint* c, word_t* w) {
         static_for<0, NW>([&](auto K) { w[K] = 0; });
         static_for<0, N>([&](auto I) {
             constexpr int i = I;
             constexpr int o = RADIX * i, wi = o / 64, sh = o % 64;
             if constexpr (wi < NW) {
-                w[wi] |= c[i] << sh;
-                if constexpr (sh + RADIX > 64 && wi + 1 < NW) w[wi + 1] |= c[i] >> (64 - sh);
+                w[wi] |= (word_t)c[i] << sh;
+                if constexpr (sh + RADIX > 64 && wi + 1 < NW) w[wi + 1] |= (word_t)c[i] >> (64 - sh);
             }
         });
     }
     // returns 1 if the value was < p (pseudo.py:1130-1146)
-    static MA_DEV int modimp_words(const spint* w, spint* a) {
+    static MA_DEV int modimp_words(const word_t* w, spint* a) {
         limbs_from_words(w, a);
         int res = (int)modfsb(a);
         nres(a, a);
         return res;
     }
     // pseudo.py:1115-1127
-    static MA_DEV void modexp_words(const spint* a, spint* w) {
+    static MA_DEV void modexp_words(const spint* a, word_t* w) {
         spint c[N];
         redc(a, c);
         words_from_limbs(c, w);

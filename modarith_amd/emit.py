@@ -27,6 +27,9 @@ EXTRA_PRIMES = ("NIST521", "PM266", "PM383", "NUMS256W", "NIST384", "NIST224", "
                 "SIDH610", "SIDH751", "MFP4", "MFP7", "MFP1973", "CSIDH512", "GM378",
                 "PM383M", "PM266M", "PM336M", "C41417M", "PM512M", "M607")
 BUILT_PRIMES = CORE_PRIMES + EXTRA_PRIMES
+# the 32-bit word form (`pseudo.py 32` / `monty.py 32`: spint = uint32_t, dpint = uint64_t) is built for the BASELINE primes; its
+# parameter structs are csrc/generated/w32_<PRIME>.h (struct P_<PRIME>_W32 in namespace ma32), its C-ABI units csrc/capi_<PRIME>_w32.hip
+W32_PRIMES = CORE_PRIMES
 
 
 # ------------------------------------------------------------------ addition chain
@@ -246,12 +249,18 @@ def _switch(name: str, ctype: str, values, fmt) -> str:
     return "    static constexpr %s %s(int i) { switch (i) { %s default: return 0; } }" % (ctype, name, body)
 
 
+def struct_name(fp: FieldParams) -> str:
+    return "P_%s" % fp.name if fp.wl == 64 else "P_%s_W%d" % (fp.name, fp.wl)
+
+
 def split_point(fp: FieldParams) -> int:
     """Bit position H at which csrc/field.h's FAST product path cuts operands into 32-bit halves, or 0 if the
     three 64-bit column accumulators (s0 + s1*2^H + s2*2^2H) cannot be proven overflow-free for this prime.
     Contract: every limb < 2^(radix+2) (tight limbs, [p,2p) with the top limb unmasked, generic=False sums);
     pre-multiplied operands (ma = mm*a, ta = 2a) are wider by bits(mm) / 1 bit.  n = most products per column."""
     W = fp.radix + 2
+    if fp.wl != 64:
+        return 0                # 32-bit words: a limb product is one 32 x 32 -> 64 multiply-add already, there is nothing to cut
     if fp.pm or fp.bad_overflow:
         return 0                # monty.py's PM form / pseudo.py's bad_overflow form: exact products only
     if fp.family == "pseudo":
@@ -346,9 +355,17 @@ def header_text(fp: FieldParams) -> str:
     L.append("// GENERATED by modarith_amd/emit.py from modarith_amd/params.py -- do not edit.")
     L.append("// prime %s = %s, family %s" % (fp.name, hex(fp.p), fp.family))
     L.append("#pragma once")
+    if fp.wl != 64:
+        L.append("// word length %d: spint = uint%d_t, dpint = uint%d_t (field.h MA_WL)" % (fp.wl, fp.wl, 2 * fp.wl))
+        L.append("#ifndef MA_WL")
+        L.append("#define MA_WL %d" % fp.wl)
+        L.append("#endif")
+        L.append("#if MA_WL != %d" % fp.wl)
+        L.append('#error "this parameter struct is for word length %d: a translation unit holds one word length"' % fp.wl)
+        L.append("#endif")
     L.append('#include "../field.h"')
-    L.append("namespace ma {")
-    L.append("struct P_%s {" % fp.name)
+    L.append("namespace %s {" % ("ma" if fp.wl == 64 else "ma%d" % fp.wl))
+    L.append("struct %s {" % struct_name(fp))
     L.append('    static constexpr const char* NAME = "%s";' % fp.name)
     L.append("    static constexpr int N = %d, RADIX = %d, NBITS = %d, NBYTES = %d, XCESS = %d, PM1D2 = %d;"
              % (N, fp.radix, fp.n, fp.nbytes, fp.xcess, fp.pm1d2))
@@ -367,8 +384,8 @@ def header_text(fp: FieldParams) -> str:
     L.append("    static constexpr unsigned long long NDASH = %s;" % _hexu(fp.ndash))
     L.append("    static constexpr int TRIN = %d, NEG_LIMB = %d;" % (fp.trin, neg[0] if neg else 0))
     br = (1 << (fp.n + fp.radix)) // fp.p if fp.montgomery else 0
-    L.append("    static constexpr unsigned long long BARRETT_R = %s;  // floor(2^(n+Radix)/p) (monty.py:923)" % _hexu(br if br < 1 << 64 else 0))
-    L.append("    static constexpr int BARRETT_SHIFT = %d;                 // (n-64) %% Radix (monty.py:930)" % ((fp.n - 64) % fp.radix))
+    L.append("    static constexpr unsigned long long BARRETT_R = %s;  // floor(2^(n+Radix)/p) (monty.py:923)" % _hexu(br if br < 1 << fp.wl else 0))
+    L.append("    static constexpr int BARRETT_SHIFT = %d;                 // (n-%d) %% Radix (monty.py:930)" % ((fp.n - fp.wl) % fp.radix, fp.wl))
     ppw = fp.ppw if fp.ppw else [0]
     L.append(_switch("ppw", "long long", ppw, lambda v: "%dll" % v if (abs(v) < 10 or v < 0) else ("0x%xll" % v)))
     r2 = fp.r2 if fp.r2 else [0] * N
@@ -401,7 +418,7 @@ def header_text(fp: FieldParams) -> str:
         L.append(_binary_cpp(fp.pe, N))
         L.append("    }")
     L.append("};")
-    L.append("}  // namespace ma")
+    L.append("}  // namespace %s" % ("ma" if fp.wl == 64 else "ma%d" % fp.wl))
     return "\n".join(L) + "\n"
 
 
@@ -450,6 +467,15 @@ def field_table_text(primes=BUILT_PRIMES) -> str:
     rows = []
     for name in primes:
         fp = derive(name)
+        rows.append('    {"%s", %d, %d, %d, %d, %d},' % (name, fp.nlimbs, fp.radix, fp.n, fp.nbytes, 1 if fp.montgomery else 0))
+    return "// GENERATED by modarith_amd/emit.py -- do not edit.\n" + "\n".join(rows) + "\n"
+
+
+def w32_table_text(primes=None) -> str:
+    """rows of modarith_amd_w32_field_info(): the macro block of each prime's field.c at word length 32"""
+    rows = []
+    for name in (primes or W32_PRIMES):
+        fp = derive(name, wl=32)
         rows.append('    {"%s", %d, %d, %d, %d, %d},' % (name, fp.nlimbs, fp.radix, fp.n, fp.nbytes, 1 if fp.montgomery else 0))
     return "// GENERATED by modarith_amd/emit.py -- do not edit.\n" + "\n".join(rows) + "\n"
 
@@ -597,6 +623,8 @@ def field_shim_text(fp: FieldParams, tag: str = None) -> str:
     edwards.c:19-23 @field@, weierstrass.c:16-20, edge.c:5-9): the macro block at the top of the generated field.c
     (pseudo.py:1388-1411, monty.py:1859-1882) with this driver's values, and the 32 undecorated names of pseudo.py:1413-1445
     mapped onto the library's <fn>_<PRIME>_ct entry points (the names decoration=True gives them, pseudo.py:1940-1944)."""
+    if fp.wl == 32:
+        return _field_shim_text_w32(fp)
     tag = tag or fp.name
     L = ["/* include/field_%s.h -- EMITTED by modarith_amd/emit.py field_shim_text(); do not edit." % tag,
          " *",
@@ -640,8 +668,62 @@ def field_shim_text(fp: FieldParams, tag: str = None) -> str:
     return "\n".join(L)
 
 
+def _field_shim_text_w32(fp: FieldParams) -> str:
+    """include/field_<PRIME>_w32.h: the same paste marker for the 32-bit word form -- the macro block of `pseudo.py 32` / `monty.py 32`
+    and the 32 names mapped onto the <fn>_<PRIME>_w32_ct entry points of include/modarith_amd_w32.h"""
+    tag = "%s_w32" % fp.name
+    L = ["/* include/field_%s.h -- EMITTED by modarith_amd/emit.py field_shim_text(); do not edit." % tag,
+         " *",
+         " * The 32-bit word form of field_%s.h (Wordlength 32: spint = uint32_t, dpint = uint64_t, the limbs of the reference's" % fp.name,
+         " * `%s 32 %s` and of simd/%s's field.cu).  Put  #include \"field_%s.h\"  where the" % (
+             "monty.py" if fp.montgomery else "pseudo.py", fp.name, "monty_cuda.py" if fp.montgomery else "pseudo_cuda.py", tag),
+         " * reference's templates say \"paste field.c here\" and link libmodarith_amd.so: modmul(a, b, c) ... then run on the GPU one",
+         " * element at a time (host pointers, the reference's signatures and aliasing rules; throughput comes from the",
+         " * <fn>_%s_batch entry points of modarith_amd_w32.h)." % tag,
+         " * prime %s = %s, %s" % (fp.name, hex(fp.p), "monty.py form" if fp.montgomery else "pseudo.py form"),
+         " */",
+         "#ifndef MODARITH_AMD_FIELD_%s_H" % tag.upper(),
+         "#define MODARITH_AMD_FIELD_%s_H" % tag.upper(),
+         "#include <stdio.h>",
+         "#include <stdint.h>",
+         '#include "modarith_amd_w32.h"',
+         "",
+         "#define sspint int32_t",
+         "#define spint uint32_t",
+         "#define dpint uint64_t",
+         "#define sdpint int64_t",
+         "#define Wordlength 32",
+         "#define Nlimbs %d" % fp.nlimbs,
+         "#define Radix %d" % fp.radix,
+         "#define Nbits %d" % fp.n,
+         "#define Nbytes %d" % fp.nbytes,
+         ""]
+    if fp.montgomery:
+        L.append("#define MONTGOMERY")
+        L.append("#define %s" % fp.name.upper())
+        if fp.trin > 0:
+            L.append("#define MULBYINT")
+    else:
+        L += ["#define MERSENNE", "#define MULBYINT", "#define %s" % fp.name]
+    L.append("")
+    L += ["#define %s %s_%s_ct" % (fn, fn, tag) for fn in FIELD_C_NAMES]
+    L += ["", "#endif", ""]
+    return "\n".join(L)
+
+
 def emit_field_shims(primes=CORE_PRIMES, out_dir: str = INCLUDE_DIR) -> List[str]:
     return [_write(os.path.join(out_dir, "field_%s.h" % name), field_shim_text(derive(name))) for name in primes]
+
+
+def emit_w32(out_dir: str = GEN_DIR, include_dir: str = INCLUDE_DIR) -> List[str]:
+    """parameter structs, field-info rows and paste-marker shims of the 32-bit word form"""
+    paths = [_write(os.path.join(out_dir, "w32_field_table.inc"), w32_table_text())]
+    for name in W32_PRIMES:
+        fp = derive(name, wl=32)
+        paths.append(_write(os.path.join(out_dir, "w32_%s.h" % name), header_text(fp)))
+        if include_dir:
+            paths.append(_write(os.path.join(include_dir, "field_%s_w32.h" % name), field_shim_text(fp)))
+    return paths
 
 
 def emit_all(primes=BUILT_PRIMES, out_dir: str = GEN_DIR) -> List[str]:
@@ -672,6 +754,7 @@ def emit_all(primes=BUILT_PRIMES, out_dir: str = GEN_DIR) -> List[str]:
         paths.append(path)
     if out_dir == GEN_DIR:
         paths += emit_field_shims()
+        paths += emit_w32()
     return paths
 
 

@@ -3,7 +3,7 @@
 Same function names, argument order and meaning as the generated field.c
 (function list pseudo.py:1413-1445 / monty.py:1885-1918), with `spint x[Nlimbs]` widened to a batch:
 a torch int64 tensor of shape [Nlimbs, n] resident in HBM (limb-interleaved SoA; int64 is only the
-64-bit container, the limbs are unsigned).  Every method launches hand-written HIP kernels through
+64-bit container, the limbs are unsigned; int32 for the 32-bit word form, `Field(prime, wl=32)`).  Every method launches hand-written HIP kernels through
 the C-ABI of include/modarith_amd.h on torch's current stream; torch is used for device memory and
 streams only.  As in the reference, outputs may alias inputs (`out=a`).
 
@@ -68,14 +68,27 @@ class Field:
         least two whole tiles and n is a multiple of the tile (n >= 2 * tile and n % tile == 0); every other n gives the FLAT 2-D
         tensor [N, n].  So `uniform(8192)` is [2, N, 4096] and `uniform(8191)` is [N, 8191].
       * `Field(prime, tile=None)`: always flat [N, n] -- what a script that indexes `[limb, j]` or labels its numbers "flat" must ask for.
-    Every method ACCEPTS both forms; `to_flat` / `to_tiled` convert; `creates_tiled(n)` tells which one n gets."""
+    Every method ACCEPTS both forms; `to_flat` / `to_tiled` convert; `creates_tiled(n)` tells which one n gets.
+
+    Word length: `Field(prime, wl=32)` is the 32-bit word form of X25519, NIST256 and X448 (include/modarith_amd_w32.h: the limbs of
+    the reference's `pseudo.py 32` / `monty.py 32`, 9 x 29, 9 x 29 and 16 x 28 bits) on torch.int32 tensors of the same shapes.  It has
+    every method of the 64-bit form except modmuls, the _lazy forms and time_protocol (NotImplementedError).  wl=64 is the default."""
 
     DEFAULT_TILE = 4096            # = modarith_amd_recommended_ld(n) for n >= 2 * 4096 (include/modarith_amd.h "TILED")
 
-    def __init__(self, prime: str, device: Optional[torch.device] = None, tile: Optional[int] = DEFAULT_TILE):
+    def __init__(self, prime: str, device: Optional[torch.device] = None, tile: Optional[int] = DEFAULT_TILE, wl: int = 64):
         self.lib = _lib.load()
         self.flib = self.lib                   # the library that holds this prime's entry points
-        if prime in _lib.PRIMES:
+        if wl not in (64, 32):
+            raise ValueError("word length must be 64 or 32")
+        self.wl = wl
+        # the container of a limb (the limbs are unsigned), its numpy view, and what the entry points of this word length are called
+        self.dtype, self._np, self._sfx = (torch.int64, np.uint64, "") if wl == 64 else (torch.int32, np.uint32, "_w32")
+        if wl == 32:
+            if prime not in _lib.W32_PRIMES:
+                raise ValueError("the 32-bit word form is built for %s (got %r); every other field is 64-bit only" % (", ".join(_lib.W32_PRIMES), prime))
+            self.params: FieldParams = derive(prime, wl=32)
+        elif prime in _lib.PRIMES:
             self.params: FieldParams = derive(prime)
         else:
             # a field made by the generator mode (modarith_amd.generate): its kernels live in a plug-in next to the main library
@@ -130,8 +143,8 @@ class Field:
 
     def empty(self, n: int) -> torch.Tensor:
         if self.creates_tiled(n):
-            return torch.empty((n // self.tile, self.N, self.tile), dtype=torch.int64, device=self.device)
-        return torch.empty((self.N, n), dtype=torch.int64, device=self.device)
+            return torch.empty((n // self.tile, self.N, self.tile), dtype=self.dtype, device=self.device)
+        return torch.empty((self.N, n), dtype=self.dtype, device=self.device)
 
     def to_tiled(self, t: torch.Tensor, tile: Optional[int] = None) -> torch.Tensor:
         """flat [N, n] -> tiled [n / tile, N, tile] (a copy; torch ops only)"""
@@ -143,14 +156,14 @@ class Field:
 
     def from_limbs(self, limbs: Sequence[Sequence[int]]) -> torch.Tensor:
         """list of per-element limb lists -> device batch [N, n] (tiled if this object creates tiled batches)."""
-        arr = np.array(limbs, dtype=np.uint64).reshape(len(limbs), self.N).T.copy()
-        t = torch.from_numpy(arr.view(np.int64)).to(self.device)
+        arr = np.array(limbs, dtype=self._np).reshape(len(limbs), self.N).T.copy()
+        t = torch.from_numpy(arr.view(np.int64 if self.wl == 64 else np.int32)).to(self.device)
         if self.creates_tiled(t.shape[1]):
             t = self.to_tiled(t)
         return t
 
     def to_limbs(self, t: torch.Tensor) -> List[List[int]]:
-        arr = self.to_flat(t.detach()).cpu().numpy().view(np.uint64)
+        arr = self.to_flat(t.detach()).cpu().numpy().view(self._np)
         return [[int(v) for v in arr[:, j]] for j in range(arr.shape[1])]
 
     def from_ints(self, xs: Iterable[int]) -> torch.Tensor:
@@ -163,21 +176,27 @@ class Field:
     def from_aos(self, aos: torch.Tensor) -> torch.Tensor:
         """element-major device array int64 [n, N] (`spint x[n][Nlimbs]`, how CPU callers of field.c hold
         elements) -> limb-interleaved batch [N, n], converted on the device."""
-        if aos.dtype != torch.int64 or aos.dim() != 2 or aos.shape[1] != self.N or not aos.is_cuda or not aos.is_contiguous():
-            raise ValueError("expected a contiguous int64 device tensor of shape [n, %d]" % self.N)
+        if aos.dtype != self.dtype or aos.dim() != 2 or aos.shape[1] != self.N or not aos.is_cuda or not aos.is_contiguous():
+            raise ValueError("expected a contiguous %s device tensor of shape [n, %d]" % (self.dtype, self.N))
         n = aos.shape[0]
         out = self.empty(n)
-        _lib.check(self.lib.modarith_amd_aos_to_soa(aos.data_ptr(), out.data_ptr(), n, self.N, max(self._ld(out), 1), _stream(self.device)), "aos_to_soa")
+        _lib.check(self._util("aos_to_soa")(aos.data_ptr(), out.data_ptr(), n, self.N, max(self._ld(out), 1), _stream(self.device)), "aos_to_soa")
         return out
 
     def to_aos(self, soa: torch.Tensor) -> torch.Tensor:
         """limb-interleaved batch [N, n] -> element-major int64 [n, N], on the device."""
         n = self._chk(soa)
-        out = torch.empty((n, self.N), dtype=torch.int64, device=soa.device)
-        _lib.check(self.lib.modarith_amd_soa_to_aos(soa.data_ptr(), out.data_ptr(), n, self.N, self._ld(soa), _stream(self.device)), "soa_to_aos")
+        out = torch.empty((n, self.N), dtype=self.dtype, device=soa.device)
+        _lib.check(self._util("soa_to_aos")(soa.data_ptr(), out.data_ptr(), n, self.N, self._ld(soa), _stream(self.device)), "soa_to_aos")
         return out
 
     # ------------------------------------------------------------------ plumbing
+    def _util(self, name: str):
+        return getattr(self.lib, "modarith_amd%s_%s" % (self._sfx, name))
+
+    def _absent(self, what: str):
+        raise NotImplementedError("%s is not offered at word length %d (include/modarith_amd_w32.h); use Field(%r) for it" % (what, self.wl, self.prime))
+
     def _ld(self, t: torch.Tensor) -> int:
         """the limb stride argument of the C-ABI: the row stride of a flat batch, the tile size of a tiled one"""
         if t.dim() == 3:
@@ -191,8 +210,8 @@ class Field:
             if N != self.N or tile < 128 or tile & (tile - 1):
                 raise ValueError("tiled batches have shape [ntiles, %d, tile] with tile a power of two >= 128" % self.N)
             for t in ts:
-                if t.dtype != torch.int64 or t.shape != t0.shape or not t.is_contiguous():
-                    raise ValueError("all operands of one call must be contiguous int64 tiled batches of one shape")
+                if t.dtype != self.dtype or t.shape != t0.shape or not t.is_contiguous():
+                    raise ValueError("all operands of one call must be contiguous %s tiled batches of one shape" % self.dtype)
                 if not t.is_cuda:
                     raise ValueError("batches must live in device memory")
                 if t.device != self.device:
@@ -200,8 +219,8 @@ class Field:
             return nt * tile
         n = t0.shape[1]
         for t in ts:
-            if t.dtype != torch.int64 or t.dim() != 2 or t.shape[0] != self.N or t.shape[1] != n:
-                raise ValueError("expected int64 tensors of shape [%d, n]" % self.N)
+            if t.dtype != self.dtype or t.dim() != 2 or t.shape[0] != self.N or t.shape[1] != n:
+                raise ValueError("expected %s tensors of shape [%d, n]" % (self.dtype, self.N))
             if not t.is_cuda:
                 raise ValueError("batches must live in device memory")
             if t.device != self.device:
@@ -217,9 +236,11 @@ class Field:
         return n
 
     def _call(self, fn: str, *args):
-        f = getattr(self.flib, "%s_%s_batch" % (fn, self.prime))
+        if self.wl == 32 and fn in _lib.W32_ABSENT:
+            self._absent(fn)
+        f = getattr(self.flib, "%s_%s%s_batch" % (fn, self.prime, self._sfx))
         with torch.cuda.device(self.device):          # the C-ABI launches on the calling thread's current device
-            _lib.check(f(*args), "%s_%s_batch" % (fn, self.prime))
+            _lib.check(f(*args), "%s_%s%s_batch" % (fn, self.prime, self._sfx))
 
     def _out(self, like: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
         # a fresh result takes the operand's limb stride (views of wider batches keep theirs), as one call needs
@@ -256,6 +277,8 @@ class Field:
 
     def modmuls(self, a, b0: Sequence[int], out=None):
         """shared multiplicand: out[j] = a[j] * b0 (one element, limbs on the host)."""
+        if self.wl == 32:
+            self._absent("modmuls")
         out = self._out(a, out)
         n = self._chk(a, out)
         host = (_lib.ctypes.c_uint64 * self.N)(*[int(v) for v in b0])
@@ -276,7 +299,7 @@ class Field:
     def modinv(self, x, h=None, out=None):
         out = self._out(x, out)
         n = self._chk(x, out) if h is None else self._chk(x, h, out)
-        if h is None and out.data_ptr() == x.data_ptr() and n >= 4096:
+        if h is None and out.data_ptr() == x.data_ptr() and n >= 4096 and self.wl == 64:
             # in place on a large batch: the simultaneous inversion needs n elements of scratch for its prefix products.  Taken from
             # torch's caching allocator here (visible to it, stream-ordered, reusable) rather than from the library's own pool:
             # the result is computed into a temporary and copied back (the kernel is VALU-bound; the copy is noise)
@@ -407,6 +430,8 @@ class Field:
         """The reference's time.c chains (pseudo.py:1177-1386) per lane, in registers: kind "modmul"
         (outer*1000 dependent modmul on x,y), "modsqr" (outer*1000 modsqr), "modinv" (outer*2 modinv).
         x, y: plain limbs (time.c applies nres itself).  Returns redc(z); z[0] & 0xFFFFFF is the check word."""
+        if self.wl == 32:
+            self._absent("time_protocol")
         k = {"modmul": 0, "modsqr": 1, "modinv": 2}[kind]
         y = x if y is None else y
         z = torch.empty_like(x)

@@ -128,8 +128,8 @@ def generate(prime: str, wl: int = 64, family: Optional[str] = None, name: Optio
     """derive the constants of `prime`, emit them, compile the kernels for it; returns the plug-in to load.
     An existing plug-in is reused when neither the constants nor any kernel source it was compiled from have changed."""
     if wl != 64:
-        raise GenerateError("only 64-bit words are built for the GPU (u64 limbs, 128-bit column sums); the reference's 16- and "
-                            "32-bit forms have no counterpart here")
+        raise GenerateError("the generator mode builds 64-bit words only (u64 limbs, 128-bit column sums); the 32-bit form exists for the "
+                            "built-in X25519, NIST256 and X448 (Field(P, wl=32), include/modarith_amd_w32.h), the 16-bit form not at all")
     fp = resolve(prime, family, name, radix)
     tag = fp.name
     from . import _lib

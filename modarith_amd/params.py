@@ -13,15 +13,17 @@ non-canonical (< 2p) results of the kernels are bit-identical to the reference's
   both            : Nbytes, PM1D2 (2-adicity of p-1), PE (progenitor exponent), root of unity.
 
 tests/test_params.py checks every value against the macro block / constants captured from the
-reference (tests/golden/field_*.json "params").  Only 64-bit words are supported: the MI355X kernels
-use u64 limbs with u128 column accumulators (SURVEY 8 sizes).
+reference (tests/golden/field_*.json "params").  The word length is a parameter of the derivation, as it is the first argument
+of the reference generators: 64 (the default: u64 limbs with u128 column accumulators, SURVEY 8 sizes, every built prime) or 32
+(u32 limbs with u64 columns, the form of simd/pseudo_cuda.py's field.cu; built for the three BASELINE primes, emit.W32_PRIMES;
+tests/test_params_w32.py checks those against tests/golden/field_w32_*.json "params").
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
 from typing import List, Optional
 
-WL = 64
+WL = 64                     # the default word length
 
 # named primes of the hot-path configs (pseudo.py:1498-1548, monty.py:1966-2062) + a few neighbours
 NAMED = {
@@ -130,6 +132,7 @@ class FieldParams:
     # derived for both families: non-zero prime limbs as (index, sign, magnitude) with the virtual
     # limb folded into limb nlimbs-1 as +2^radix (caddp/addp/subp: pseudo.py:202-220, monty.py:301-349)
     pp: List[tuple] = field(default_factory=list)
+    wl: int = 64                # word length the derivation was made for (spint = u64 | u32)
 
     @property
     def montgomery(self) -> bool:
@@ -178,7 +181,7 @@ def _root_of_unity(p: int, k: int) -> int:
 
 
 # ------------------------------------------------------------------ pseudo-Mersenne (2^n - m)
-def _pm_radix(n: int) -> int:
+def _pm_radix(n: int, WL: int = WL) -> int:
     """smallest limb count whose worst-case column sum fits 2*WL bits, radix <= WL-3
     (rule of pseudo.py:124-140)."""
     limbs = n // WL
@@ -193,11 +196,12 @@ def _pm_radix(n: int) -> int:
             return radix
 
 
-def derive_pseudo(name: str, p: int, radix: Optional[int] = None) -> FieldParams:
+def derive_pseudo(name: str, p: int, radix: Optional[int] = None, wl: int = WL) -> FieldParams:
+    WL = wl
     n = p.bit_length()
     if n < 120 or pow(3, p - 1, p) != 1:
         raise ValueError("not a sensible modulus")
-    radix = radix or _pm_radix(n)
+    radix = radix or _pm_radix(n, WL)
     m = (1 << n) - p
     b = 1 << radix
     if m >= b:
@@ -216,7 +220,7 @@ def derive_pseudo(name: str, p: int, radix: Optional[int] = None) -> FieldParams
     k, pe = _two_adic(p)
     fp = FieldParams(name=name, family="pseudo", p=p, n=n, radix=radix, nlimbs=N, xcess=xcess,
                      nbytes=-(-n // 8), pm1d2=k, pe=pe, roi=_makebig(_root_of_unity(p, k), radix, N),
-                     m=m, mm=mm, tw=tw, overflow=overflow, bad_overflow=bad_overflow, fred=fred, epm=epm, carry_on=carry_on)
+                     m=m, mm=mm, tw=tw, overflow=overflow, bad_overflow=bad_overflow, fred=fred, epm=epm, carry_on=carry_on, wl=WL)
     fp.pp = [(0, -1, m), (N - 1, +1, tw)]
     return fp
 
@@ -251,7 +255,7 @@ def _signed_limbs(p: int, radix: int, N: int, pm_m: int = 0):
     return out, bool(carry)
 
 
-def _monty_radix(p: int, n: int) -> int:
+def _monty_radix(p: int, n: int, WL: int = WL) -> int:
     """default radix rule of monty.py:151-173: at least two spare bits in the top limb, or none at
     all together with a virtual limb."""
     limbs = n // WL
@@ -291,11 +295,12 @@ def _trinomial(p: int, radix: int) -> int:
     return k // radix if k % radix == 0 else 0
 
 
-def derive_monty(name: str, p: int, radix: Optional[int] = None) -> FieldParams:
+def derive_monty(name: str, p: int, radix: Optional[int] = None, wl: int = WL) -> FieldParams:
+    WL = wl
     n = p.bit_length()
     if n < 120 or pow(3, p - 1, p) != 1:
         raise ValueError("not a sensible modulus")
-    radix = radix or _monty_radix(p, n)
+    radix = radix or _monty_radix(p, n, WL)
     b = 1 << radix
     N = -(-n // radix)
     xcess = N * radix - n
@@ -312,7 +317,7 @@ def derive_monty(name: str, p: int, radix: Optional[int] = None) -> FieldParams:
     fp = FieldParams(name=name, family="monty", p=p, n=n, radix=radix, nlimbs=N, xcess=xcess,
                      nbytes=-(-n // 8), pm1d2=k, pe=pe, roi=_makebig(_root_of_unity(p, k), radix, N),
                      m=m, ppw=ppw, E=E, R=R, ndash=ndash, r2=_makebig(R * R % p, radix, N),
-                     trin=_trinomial(p, radix), pm=pm)
+                     trin=_trinomial(p, radix), pm=pm, wl=WL)
     pp = [(i, -1 if v < 0 else +1, abs(v)) for i, v in enumerate(ppw[:N]) if v]
     if E:
         # fold +1 * 2^(radix*N) into limb N-1 as +2^radix
@@ -323,8 +328,10 @@ def derive_monty(name: str, p: int, radix: Optional[int] = None) -> FieldParams:
     return fp
 
 
-def derive(name: str, family: Optional[str] = None, radix: Optional[int] = None) -> FieldParams:
-    """FieldParams for a named prime (or a python expression such as '2**255-19')."""
+def derive(name: str, family: Optional[str] = None, radix: Optional[int] = None, wl: int = WL) -> FieldParams:
+    """FieldParams for a named prime (or a python expression such as '2**255-19') at word length wl (64 | 32)."""
+    if wl not in (32, 64):
+        raise ValueError("word length must be 64 or 32")
     if name in NAMED:
         p, fam = NAMED[name]
     else:
@@ -333,6 +340,6 @@ def derive(name: str, family: Optional[str] = None, radix: Optional[int] = None)
     if fam is None:
         n = p.bit_length()
         fam = "pseudo" if ((1 << n) - p) < (1 << 32) else "monty"
-    if radix is None and fam == "monty":
+    if radix is None and fam == "monty" and wl == 64:
         radix = RADIX_64.get(name)
-    return derive_pseudo(name, p, radix) if fam == "pseudo" else derive_monty(name, p, radix)
+    return derive_pseudo(name, p, radix, wl) if fam == "pseudo" else derive_monty(name, p, radix, wl)
