@@ -23,8 +23,12 @@
  * NIST256) or 64 bytes (X448).  Per-lane access width: 16 bytes (four elements per lane) for the 9-limb fields and 8 bytes (two)
  * for X448 when every buffer is 16- / 8-byte aligned and ld is a multiple of 4 / 2; 4 bytes otherwise.  Same results on every path.
  * One product policy: a 32-bit limb product is one 32 x 32 -> 64 multiply-add into a 64-bit column, the reference's own dpint
- * arithmetic -- exact for every limb pattern, no limb contract.  modinv returns the NORMALISED inverse nres(redc(1/x)) as at 64 bits
- * (one inversion per element here).  Ownership, aliasing (an output may be an input: modmul(a, a, a), modsqr(a, a)), errors, streams
+ * arithmetic -- exact for every limb pattern, no limb contract.  modinv returns the NORMALISED inverse nres of redc of 1/x as at 64
+ * bits; without progenitors and from 32 768 elements on, the batched modinv shares one inversion between up to 64 elements
+ * (Montgomery's simultaneous inversion; in place it takes stream-ordered scratch of the library's own, and under stream capture or
+ * with MA_INV_SIMUL=0 it keeps one inversion per element) -- the same words either way, for every limb pattern; which path ran is
+ * what modarith_amd_last_launch reports.  Sequences of calls per element fuse into one kernel through modarith_amd/fuse.py at this
+ * word length too (plug-ins exporting chain_<name>_<PRIME>_w32_batch).  Ownership, aliasing (an output may be an input: modmul(a, a, a), modsqr(a, a)), errors, streams
  * and threading: as in modarith_amd.h.  MODARITH_AMD_ABI is unchanged by this header: nothing existing changed.
  */
 #ifndef MODARITH_AMD_W32_H

@@ -134,12 +134,37 @@ int BATCH(nres)(const ma_spint32* a, ma_spint32* c, size_t n, size_t ld, void* s
 int BATCH(redc)(const ma_spint32* a, ma_spint32* c, size_t n, size_t ld, void* st) { return launch_unary<OpRedc<P>>(a, c, n, ld, st, "redc(w32)"); }
 int BATCH(modpro)(const ma_spint32* a, ma_spint32* c, size_t n, size_t ld, void* st) { return launch_unary_heavy<OpPro<P>>(a, c, n, ld, st, "modpro(w32)"); }
 
-// one inversion per element (the simultaneous-inversion kernel of the 64-bit form has no counterpart here yet); outputs in the
-// normalised form nres(redc(1/x)), as at 64 bits
+// Large batches without a caller-supplied progenitor: simultaneous inversion (kernels32.h k_inv_simul), one modinv per up to 64
+// elements, dispatched as the 64-bit form does it (capi_prime.inc): the prefix products go to the output buffer, or -- when the
+// output IS the input -- to stream-ordered scratch of the library's own (not during stream capture; without scratch the per-element
+// kernel runs).  MA_INV_SIMUL=0 keeps one modinv per element.  Same words either way: outputs in the normalised form
+// nres(redc(1/x)), as at 64 bits.  The thresholds are the 64-bit form's.
+constexpr size_t INV_SIMUL_LANES = 16384;      // lanes kept busy before elements start sharing an inversion
+constexpr size_t INV_SIMUL_MIN = 32768;        // batches from this size on share inversions
 int BATCH(modinv)(const ma_spint32* x, const ma_spint32* h, ma_spint32* z, size_t n, size_t ld, void* st) {
     if (n == 0) return 0;
-    if (h == nullptr) return launch_unary_heavy<OpInv<P>>(x, z, n, ld, st, "modinv(w32)");
     MA_LD("modinv(w32)")
+    if (h == nullptr && n >= INV_SIMUL_MIN && ma::inv_simul()) {
+        hipStream_t s = (hipStream_t)st;
+        size_t rounds = (n + INV_SIMUL_LANES - 1) / INV_SIMUL_LANES;
+        if (rounds > 64) rounds = 64;
+        const size_t lanes = (n + rounds - 1) / rounds;
+        const unsigned grid = (unsigned)((lanes + BLOCK - 1) / BLOCK);
+        if (x != z) {
+            k_inv_simul<P><<<grid, BLOCK, 0, s>>>(x, z, z, n, lanes, (int)rounds, L, L, L);
+            return check_launch("modinv(w32, simultaneous)");
+        }
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (s == nullptr || (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone)) {
+            if (spint* ws = static_cast<spint*>(ma::scratch_alloc(n * NL * sizeof(spint), s))) {
+                k_inv_simul<P><<<grid, BLOCK, 0, s>>>(x, z, ws, n, lanes, (int)rounds, L, L, Ld(n));
+                ma::scratch_free(ws, s);
+                return check_launch("modinv(w32, simultaneous, in place)");
+            }
+        }
+        (void)hipGetLastError();
+    }
+    if (h == nullptr) return launch_unary_heavy<OpInv<P>>(x, z, n, ld, st, "modinv(w32)");
     k_inv_h<P><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(x, h, z, n, L, L, L);
     return check_launch("modinv(w32, h)");
 }

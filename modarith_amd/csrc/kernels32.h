@@ -161,6 +161,111 @@ __global__ __launch_bounds__(BLOCK) void k_inv_h(const spint* xs, const spint* h
         store_soa<P, 1>(zs, ldz, t, z);
     }
 }
+// In-contract predicate of the simultaneous inversion: DIGIT FORM BELOW 2^(Nbits+1) -- limbs 0..N-2 below 2^Radix and the top limb
+// below 2^TOPB, TOPB = Nbits + 1 - Radix (N-1) (24 / 25 / 29 bits for X25519 / NIST256 / X448).  Every element below 2p in digit form
+// passes (2p < 2^(Nbits+1)): that is what the field functions return and accept.  modarith_amd/params.py w32_inv_in_contract restates it.
+//
+// Why modmul(c, x) is congruent to c x (times R^-1 for Montgomery) and modis0 is exact on it, for every admitted x and every c that
+// is itself a product output or the constant one.  Write W for the operand set: limbs 0..N-2 below 2^Radix -- but limb 1 of a
+// pseudo-Mersenne product output, which is left unmasked, below 2^Radix + 2^15 -- and the top limb below 2^TOPB.  The emitted
+// arithmetic is an identity over the integers as long as no 64-bit column and no 32-bit word wraps, so only sizes have to be shown.
+//   * X25519 (pseudo.py, Radix 29, N 9, overflow form, mm = 19 * 2^6 = 1216).  Operands a, b in W.  Row r folds the products
+//     a_k b_(9+r-k), k = r+1..8.  Row 0 folds eight: a_1 b_8 and a_8 b_1 hold a top limb (< 2^(29.001+24) each), six are below
+//     (2^29 - 1)^2: tt < 6.1 * 2^58.  Rows 1..7 fold at most seven products and only limbs 2..8 meet there (k >= 2 and
+//     9 + r - k >= 2): tt <= 7 (2^29 - 1)^2.  So hi = tt >> 29 <= 7 * 2^29 - 14 fits a word -- this is what a single limb at
+//     2^31 - 1 breaks -- and lo + hi <= (2^29 - 1) + 7 * 2^29 - 14 < 2^32 does not wrap.  A column holds at most nine products
+//     (< 2^61.2), (lo + hi) mm < 2^42.3 and a carry below 2^33: < 2^62.  The second pass takes ut = 19 (64 t + (v_8 >> 23)) < 2^44
+//     with t < 2^33, leaves limb 0 masked, adds (s >> 29) + (ut >> 29) < 2^15 to limb 1 (the slack of W) and masks the top limb
+//     to 23 bits.  So a product output is in W, is congruent to a b, and its value is below 2^255 + 2^45 < 2p.
+//   * NIST256 (monty.py, Radix 29, N 9, R = 2^261).  Operands in W have limbs below 2^29.001 and a top limb below 2^25: a column holds
+//     at most nine products (< 2^61.2), the reduction adds four digit-times-prime-limb products (< 2^60), two shifted digits and a
+//     carry: < 2^62.  Nothing wraps, so c = (a b + q p) / R with q < R: c < 2^514 / 2^261 + p < 2p, in digit form by construction
+//     (limbs masked, the top limb takes the rest, below 2^25).
+//   * X448 (monty.py, Radix 28, N 16 and the virtual seventeenth limb: R = 2^476, not 2^448 -- modarith_amd/params.py derive_monty;
+//     this is where the slack above p comes from).  Limbs below 2^28.001, top limb below 2^29: a column holds at most sixteen products
+//     of which two hold a top limb (< 14 * 2^56.001 + 2^58.1 < 2^60.4), prime limbs are -1 / 0 / +1 so the reduction adds a few
+//     words: < 2^61.  c = (a b + q p) / R < 2^898 / 2^476 + p < 2p, in digit form, top limb below 2^29.
+// So every product output lies in W below 2p, whatever admitted operands it came from, and by induction every prefix c_r and the running
+// inverse do.  modis0 is redc -- the identity (pseudo) or a product by one (below p + 1) -- followed by modfsb, which is exact below
+// 2p: 1 exactly for the values 0 and p, i.e. for every representation of zero a product can return.
+template <class P> MA_DEV bool inv_in_contract(const spint* x) {
+    constexpr int TOPB = P::NBITS + 1 - P::RADIX * (P::N - 1);
+    static_assert(TOPB > 0 && TOPB <= 29 && P::RADIX <= 29, "the bounds of the comment above");
+    spint m = 0;
+    static_for<0, P::N - 1>([&](auto I) { m |= x[I]; });
+    return ((m >> P::RADIX) | (x[P::N - 1] >> TOPB)) == 0;
+}
+
+// z[j] = 1/x[j] for a whole batch with ONE inversion per `rounds` elements (Montgomery's simultaneous inversion): the 32-bit
+// counterpart of kernels.h k_inv_simul, whose header comment describes the scheme.  Lane j of L takes the elements {r * L + j}
+// (every access of a wave is one coalesced row); forward it multiplies them up and stores the prefix products c_r in cs (the output
+// buffer, or scratch when the output is the input); one Field<P>::modinv on the last prefix; backward 1/x_r = inv * c_{r-1},
+// inv *= x_r.  Outputs in the normalised form nres(redc(.)): the words of the per-element kernel (OpInv).
+// No element may spoil another.  Two kinds stay out of the running product by lane predication (c_r = c_{r-1}); their verdicts
+// travel to the backward pass in two per-lane 64-bit masks, bit r for round r (the 29-bit limbs of this form have no spare bits
+// once the top limb is unmasked, and rounds <= 64):
+//   * zero values, detected on the PRODUCT c_{r-1} * x_r where modis0 is exact whatever the representation of x_r (0, p, 2p): output 0,
+//     as the per-element kernel gives (every product of its chain is then 0 or p, and the normalisation makes that 0);
+//   * elements outside inv_in_contract (fabricated limbs: the emitted arithmetic wraps on them): an inversion of their own in the
+//     backward pass, the very function the per-element kernel runs, paid by the waves that hold one.
+template <class P>
+struct InvSimul {
+    using F = Field<P>;
+    static MA_DEV void run(const spint* xs, spint* zs, spint* cs, size_t n, size_t L, int rounds, Ld ldx, Ld ldz, Ld ldc, size_t j) {
+        spint c[P::N], x[1][P::N], t[1][P::N];
+        uint64_t zeros = 0, oocs = 0;
+        F::modone(c);
+#pragma unroll 1
+        for (int r = 0; r < rounds; r++) {
+            const size_t e = (size_t)r * L + j;
+            if (e >= n) break;                                  // (e grows with r)
+            load_soa<P, 1>(xs, ldx, e, x);
+            const bool ooc = !inv_in_contract<P>(x[0]);
+            F::modmul(c, x[0], t[0]);                           // (discarded for an out-of-contract x)
+            const bool zero = !ooc && F::modis0(t[0]) != 0;
+            const bool skip = ooc || zero;
+            static_for<0, P::N>([&](auto I) { c[I] = skip ? c[I] : t[0][I]; });
+            static_for<0, P::N>([&](auto I) { t[0][I] = c[I]; });
+            zeros |= (uint64_t)zero << r;
+            oocs |= (uint64_t)ooc << r;
+            store_soa<P, 1>(cs, ldc, e, t);
+        }
+        spint inv[P::N];
+        F::modinv(c, nullptr, inv);
+#pragma unroll 1
+        for (int r = rounds - 1; r >= 0; r--) {
+            const size_t e = (size_t)r * L + j;
+            if (e >= n) continue;
+            load_soa<P, 1>(xs, ldx, e, x);
+            const bool zero = (zeros >> r) & 1, ooc = (oocs >> r) & 1;
+            spint zi[P::N];
+            if (r > 0) {
+                load_soa<P, 1>(cs, ldc, e - L, t);
+                F::modmul(inv, t[0], zi);                       // inv * c_{r-1}
+                F::modmul(inv, x[0], t[0]);
+                static_for<0, P::N>([&](auto I) { inv[I] = (zero || ooc) ? inv[I] : t[0][I]; });
+            } else {
+                static_for<0, P::N>([&](auto I) { zi[I] = inv[I]; });
+            }
+            inv_normalise<F>(zi);
+            static_for<0, P::N>([&](auto I) { zi[I] = zero ? (spint)0 : zi[I]; });
+            if (__any(ooc)) {                                   // fabricated limbs somewhere in this wave: their own inversion
+                spint w[P::N];
+                F::modinv(x[0], nullptr, w);
+                inv_normalise<F>(w);
+                static_for<0, P::N>([&](auto I) { zi[I] = ooc ? w[I] : zi[I]; });
+            }
+            static_for<0, P::N>([&](auto I) { t[0][I] = zi[I]; });
+            store_soa<P, 1>(zs, ldz, e, t);
+        }
+    }
+};
+template <class P>
+__global__ __launch_bounds__(BLOCK) void k_inv_simul(const spint* xs, spint* zs, spint* cs, size_t n, size_t L, int rounds, Ld ldx, Ld ldz, Ld ldc) {
+    const size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j < L) InvSimul<P>::run(xs, zs, cs, n, L, rounds, ldx, ldz, ldc, j);
+}
+
 // r[j] = sqrt(x[j]) / qr(x[j]) with caller-supplied progenitors h[j] (pseudo.py:815-874)
 template <class P, bool QR>
 __global__ __launch_bounds__(BLOCK) void k_sqrt_h(const spint* xs, const spint* hs, spint* rs, int* out, size_t n, Ld ld) {

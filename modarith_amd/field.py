@@ -72,7 +72,9 @@ class Field:
 
     Word length: `Field(prime, wl=32)` is the 32-bit word form of X25519, NIST256 and X448 (include/modarith_amd_w32.h: the limbs of
     the reference's `pseudo.py 32` / `monty.py 32`, 9 x 29, 9 x 29 and 16 x 28 bits) on torch.int32 tensors of the same shapes.  It has
-    every method of the 64-bit form except modmuls, the _lazy forms and time_protocol (NotImplementedError).  wl=64 is the default."""
+    every method of the 64-bit form except modmuls, the _lazy forms and time_protocol (NotImplementedError); modinv shares one
+    inversion between up to 64 elements of a large batch as the 64-bit form does (same words as one inversion per element), and
+    modarith_amd.fuse.Chain(prime, name, wl=32) fuses sequences of calls on such batches.  wl=64 is the default."""
 
     DEFAULT_TILE = 4096            # = modarith_amd_recommended_ld(n) for n >= 2 * 4096 (include/modarith_amd.h "TILED")
 
@@ -299,7 +301,7 @@ class Field:
     def modinv(self, x, h=None, out=None):
         out = self._out(x, out)
         n = self._chk(x, out) if h is None else self._chk(x, h, out)
-        if h is None and out.data_ptr() == x.data_ptr() and n >= 4096 and self.wl == 64:
+        if h is None and out.data_ptr() == x.data_ptr() and n >= (4096 if self.wl == 64 else 32768):     # (32 768: where the 32-bit form starts sharing)
             # in place on a large batch: the simultaneous inversion needs n elements of scratch for its prefix products.  Taken from
             # torch's caching allocator here (visible to it, stream-ordered, reusable) rather than from the library's own pool:
             # the result is computed into a temporary and copied back (the kernel is VALU-bound; the copy is noise)

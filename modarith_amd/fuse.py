@@ -28,6 +28,14 @@ the exact ones.  C-ABI of the built plug-in (modarith_amd/plugins/libmodarith_am
 modmli nres redc modcpy modinv modpro modsqrt modnsqr modhaf modcmv modcsw and the generic=False forms modadd_lazy modsub_lazy
 modneg_lazy (one level of laziness between reductions, which is how rfc7748.c uses them).
 
+Word length 32: `Chain(prime, name, wl=32)` is the same chain over the 32-bit word form of X25519, NIST256 and X448 (csrc/kernels32.h,
+namespace ma32; int32 batches of `Field(prime, wl=32)`): what a port of the reference's per-thread CUDA form (simd/pseudo_cuda.py 32)
+runs per element.  One product policy, so no vote; one, two or four elements per lane (the library's pick_ept rules), by default one
+in workgroups of 256 (measured: profiles/w32_chain_rate.json, docs/fused_chains.md); every operation above except the generic=False forms, which that word length does not
+offer, and no element-major entry (convert with modarith_amd_w32_aos_to_soa).  Symbol, library and object names carry `_w32`:
+
+    int chain_<name>_<TAG>_w32_batch(const void *const *in, void *const *out, size_t n, size_t ld, void *stream);
+
 Like the generator mode (modarith_amd/generate.py) this needs hipcc where the chain is built and has no CPU path.
 """
 from __future__ import annotations
@@ -51,6 +59,13 @@ _OPS = {"modmul": 2, "modadd": 2, "modsub": 2, "modsqr": 1, "modneg": 1, "nres":
 _HEAVY = ("modinv", "modpro", "modsqrt")          # long exponentiation chains: one element per lane
 _LAZY = ("modadd_lazy", "modsub_lazy", "modneg_lazy")
 MAX_OPS = 256
+# 32-bit word form: elements per lane and workgroup size of a chain without an inversion.  Measured (tools/w32_chain_rate.py,
+# profiles/w32_chain_rate.json: the four-call chain at 2^24 elements on tiles of 4096, share of the HBM peak over its own bytes): one
+# element per lane in workgroups of 256 runs at 0.770 / 0.770 / 0.763-0.774 for X25519 / NIST256 / X448 against 0.760 / 0.780 / 0.732 at
+# two and 0.728 / 0.752 / 0.697 at four elements per lane, workgroups of 128 behind 256 at every width -- the streaming kernels'
+# shape, ahead for X25519 and X448 and 1.3 % behind two elements per lane for NIST256.  build(ept=, block=) overrides them
+W32_EPT_DEFAULT = 1
+W32_BLOCK_DEFAULT = 256
 
 
 class Val:
@@ -66,10 +81,19 @@ class Sel:
 
 
 class Chain:
-    def __init__(self, prime: str, name: str):
+    def __init__(self, prime: str, name: str, wl: int = 64):
         if not _NAME_RE.match(name):
             raise ValueError("chain name %r cannot be part of a C identifier" % (name,))
-        if prime in _lib.PRIMES:
+        if wl not in (64, 32):
+            raise ValueError("word length must be 64 or 32 (got %r)" % (wl,))
+        self.wl = wl
+        if wl == 32:
+            if prime not in _lib.W32_PRIMES:
+                raise ValueError("the 32-bit word form is built for %s (got %r); every other field is 64-bit only" % (", ".join(_lib.W32_PRIMES), prime))
+            from .params import derive
+            self.params = derive(prime, wl=32)
+            self.builtin = True
+        elif prime in _lib.PRIMES:
             from .params import derive
             self.params = derive(prime)
             self.builtin = True
@@ -132,6 +156,9 @@ class Chain:
     # generic=False forms (pseudo.py:294-302, 315-324, 337-346: what rfc7748.c:20 asks for).  Their results carry up to two extra bits;
     # one level of them keeps the limb contract the split products rely on, a lazy sum of lazy sums need not -- refused here
     def _lazy(self, op, a, b=None):
+        if self.wl == 32:
+            raise ValueError("%s is not offered at word length 32 (include/modarith_amd_w32.h: the 29-bit limbs of X25519 leave no room for "
+                             "an unreduced sum); use %s" % (op, op[:-5]))
         for v in (a, b):
             if v is not None and v.idx in self.lazy:
                 raise ValueError("%s of a value that is itself a generic=False result: reduce in between (modadd / modsub / modmul ...)" % op)
@@ -181,32 +208,29 @@ class Chain:
 
     # ------------------------------------------------------------------ emission
     def default_ept(self) -> int:
-        return 1 if any(o[0] in _HEAVY for o in self.ops) else 2
+        if any(o[0] in _HEAVY for o in self.ops):
+            return 1
+        return 2 if self.wl == 64 else W32_EPT_DEFAULT
+
+    @property
+    def _tag(self) -> str:
+        """what follows the chain's name in its symbol, library and object names"""
+        return self.prime if self.wl == 64 else self.prime + "_w32"
 
     @property
     def symbol(self) -> str:
-        return "chain_%s_%s_batch" % (self.name, self.prime)
+        return "chain_%s_%s_batch" % (self.name, self._tag)
 
     def traffic_bytes(self) -> int:
-        """HBM bytes per element of the fused kernel; the call-by-call sequence moves sum(8 N (operands + 1)) instead"""
-        return 8 * self.params.nlimbs * (self.nin + len(self.outs)) + 4 * self.nsel
+        """HBM bytes per element of the fused kernel; the call-by-call sequence moves sum(w N (operands + 1)) instead (w = 8 or 4 bytes a limb)"""
+        return (self.wl // 8) * self.params.nlimbs * (self.nin + len(self.outs)) + 4 * self.nsel
 
     def unfused_traffic_bytes(self) -> int:
-        return sum(8 * self.params.nlimbs * (_OPS[o[0]] + (2 if o[0] == "modcsw" else 1)) + (4 if o[0] in ("modcmv", "modcsw") else 0) for o in self.ops)
+        return sum((self.wl // 8) * self.params.nlimbs * (_OPS[o[0]] + (2 if o[0] == "modcsw" else 1)) + (4 if o[0] in ("modcmv", "modcsw") else 0) for o in self.ops)
 
-    def source(self, ept: Optional[int] = None, policy: str = "vote", waves: int = 0) -> str:
-        """ept: elements per lane on aligned batches (2 = 16-byte accesses, 1 = 8-byte); None = the measured default"""
-        if not self.nin or not self.outs:
-            raise ValueError("a chain needs at least one input and one output")
-        P, nv = self.prime, self.nvals
-        L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s: %d inputs, %d operations, %d outputs." % (self.name, P, self.nin, len(self.ops), len(self.outs)),
-             '#include "params_%s.h"' % P, '#include "modarith_amd.h"', '#include "capi_common.h"', '#include "kernels.h"', "",
-             "namespace {", "using namespace ma;", "using P = ma::P_%s;" % P, "constexpr int NIN = %d, NOUT = %d;" % (self.nin, len(self.outs)),
-             "constexpr bool HEAVY = %s;   // one element per lane (8-byte accesses) on every batch: chains with an inversion, as the library's k_unary_heavy" % ("true" if (ept or self.default_ept()) == 1 else "false"),
-             "constexpr int NSEL = %d;" % self.nsel,
-             "struct Args { const spint* in[NIN]; spint* out[NOUT]; const int* sel[NSEL > 0 ? NSEL : 1]; };", "",
-             "// the chain on one element's registers; F = Field<P, FAST>",
-             "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i < self.nin else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)])]
+    def _body_lines(self) -> List[str]:
+        """the chain as Field<P> calls on registers, one line per operation"""
+        L = []
         for o in self.ops:
             op, d, a, b, imm = o[:5]
             if op == "modcsw":
@@ -227,6 +251,97 @@ class Chain:
                 L.append("    F::%s(v%d, v%d, v%d);" % (op, a, b, d))
             else:
                 L.append("    F::%s(v%d, v%d);" % (op, a, d))
+        return L
+
+    def _source32(self, ept: Optional[int], waves: int, block: Optional[int]) -> str:
+        """the unit of the 32-bit word form: csrc/kernels32.h's load_soa / store_soa around body<Field<P>>, one product policy"""
+        P, nv = self.prime, self.nvals
+        heavy = any(o[0] in _HEAVY for o in self.ops)
+        cap = 1 if heavy else (ept or self.default_ept())
+        if cap not in (1, 2, 4):
+            raise ValueError("elements per lane at word length 32: 1, 2 or 4")
+        block = block or W32_BLOCK_DEFAULT
+        if block not in (64, 128, 256):
+            raise ValueError("workgroup size: 64, 128 or 256")
+        args = ", ".join(["v%d[E]" % i for i in range(nv)] + ["s%d[E]" % k for k in range(self.nsel)])
+        L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s, 32-bit word form: %d inputs, %d operations, %d outputs." % (self.name, P, self.nin, len(self.ops), len(self.outs)),
+             '#include "w32_%s.h"' % P, '#include "modarith_amd_w32.h"', '#include "capi_common.h"', '#include "kernels32.h"', "",
+             "namespace {", "using namespace ma32;", "using ma::check_launch;", "using ma::grid_for;", "using ma::set_error;", "using P = ma32::P_%s_W32;" % P,
+             "constexpr int NIN = %d, NOUT = %d, NSEL = %d;" % (self.nin, len(self.outs), self.nsel),
+             "constexpr bool HEAVY = %s;   // an inversion, a progenitor or a square root in the chain: one element per lane" % ("true" if heavy else "false"),
+             "constexpr int EPT_CAP = %d;   // widest access of this build in elements per lane (4 = 16 bytes, 2 = 8, 1 = 4); wider kernels are not instantiated" % cap,
+             "constexpr int CBLOCK = %d;   // workgroup size" % block,
+             'static_assert(!HEAVY || EPT_CAP == 1, "the long chains run one element per lane");',
+             "struct Args { const spint* in[NIN]; spint* out[NOUT]; const int* sel[NSEL > 0 ? NSEL : 1]; };", "",
+             "// the chain on one element's registers; F = Field<P> (one product policy at this word length: no vote)",
+             "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i < self.nin else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)])]
+        L += self._body_lines()
+        L += ["}", "",
+              "template <int EPT>", "__global__ __launch_bounds__(CBLOCK) %svoid k_chain(Args A, size_t nthreads, Ld L) {" % ("__attribute__((amdgpu_waves_per_eu(%d, %d))) " % (waves, waves) if waves else ""),
+              "    for (size_t t = (size_t)blockIdx.x * CBLOCK + threadIdx.x; t < nthreads; t += (size_t)gridDim.x * CBLOCK) {",
+              "        " + " ".join("spint v%d[EPT][P::N];" % i for i in range(nv))]
+        L += ["        load_soa<P, EPT>(A.in[%d], L, t, v%d);" % (i, i) for i in range(self.nin)]
+        L += ["        int s%d[EPT]; static_for<0, EPT>([&](auto E) { s%d[E] = A.sel[%d][(size_t)EPT * t + E]; });" % (k, k, k) for k in range(self.nsel)]
+        L += ["        static_for<0, EPT>([&](auto E) { body<Field<P>>(%s); });" % args]
+        L += ["        store_soa<P, EPT>(A.out[%d], L, t, v%d);" % (k, o) for k, o in enumerate(self.outs)]
+        L += ["    }", "}", "}  // namespace", "",
+              'extern "C" int %s(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) {' % self.symbol,
+              "    // in[0 .. NIN): element batches of uint32_t limbs; in[NIN .. NIN + NSEL): int32 selector arrays, one entry per element",
+              "    if (n == 0) return 0;",
+              "    Ld L(ld);",
+              "    if (ld < n) {",
+              '        if (ld < 128 || (ld & (ld - 1)) != 0) { set_error("%s: a limb stride below n selects the tiled layout and must be a power of two >= 128"); return (int)hipErrorInvalidValue; }' % self.symbol,
+              "        L = Ld(ld, (unsigned)__builtin_ctzll((unsigned long long)ld));",
+              "    }",
+              "    Args A;",
+              "    uintptr_t addr = 0;",
+              "    for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; addr |= reinterpret_cast<uintptr_t>(in[i]); }",
+              "    for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; addr |= reinterpret_cast<uintptr_t>(out[i]); }",
+              "    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + i];",
+              "    hipStream_t s = (hipStream_t)stream;",
+              "    const bool tiled = L.s != 63;",
+              "    // elements per lane (the rules of the library's pick_ept): EPT elements need n >= EPT, a stride that is a multiple of EPT and",
+              "    // 4 * EPT-byte aligned rows; what is left over (fewer than EPT elements) runs one element per lane at its own address",
+              "    int ept = 1;",
+              "    if (EPT_CAP >= 4 && n >= 4 && ld % 4 == 0 && (addr & 15u) == 0) ept = 4;",
+              "    else if (EPT_CAP >= 2 && n >= 2 && ld % 2 == 0 && (addr & 7u) == 0) ept = 2;",
+              "    const size_t nt = n / ept, done = nt * ept;",
+              "    if constexpr (EPT_CAP >= 4) if (ept == 4) k_chain<4><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, nt, L);",
+              "    if constexpr (EPT_CAP >= 2) if (ept == 2) k_chain<2><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, nt, L);",
+              "    if (ept == 1) k_chain<1><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, nt, L);",
+              "    if (done < n) {",
+              "        const size_t o = L.off<P::N>(done);",
+              "        Args B;",
+              "        for (int i = 0; i < NIN; i++) B.in[i] = A.in[i] + o;",
+              "        for (int i = 0; i < NOUT; i++) B.out[i] = A.out[i] + o;",
+              "        for (int i = 0; i < NSEL; i++) B.sel[i] = A.sel[i] + done;",
+              "        k_chain<1><<<1, CBLOCK, 0, s>>>(B, n - done, Ld(L.ld));",
+              "    }",
+              '    return check_launch("%s");' % self.symbol,
+              "}", ""]
+        return "\n".join(L)
+
+    def source(self, ept: Optional[int] = None, policy: str = "vote", waves: int = 0, block: Optional[int] = None) -> str:
+        """ept: elements per lane on aligned batches (2 = 16-byte accesses, 1 = 8-byte; at word length 32: 4 / 2 / 1 = 16 / 8 / 4 bytes);
+        None = the measured default.  block: workgroup size, word length 32 only"""
+        if not self.nin or not self.outs:
+            raise ValueError("a chain needs at least one input and one output")
+        if self.wl == 32:
+            if policy != "vote":
+                raise ValueError("word length 32 has one product policy: there is nothing to force")
+            return self._source32(ept, waves, block)
+        if block is not None:
+            raise ValueError("the workgroup size is a parameter of the 32-bit word form only")
+        P, nv = self.prime, self.nvals
+        L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s: %d inputs, %d operations, %d outputs." % (self.name, P, self.nin, len(self.ops), len(self.outs)),
+             '#include "params_%s.h"' % P, '#include "modarith_amd.h"', '#include "capi_common.h"', '#include "kernels.h"', "",
+             "namespace {", "using namespace ma;", "using P = ma::P_%s;" % P, "constexpr int NIN = %d, NOUT = %d;" % (self.nin, len(self.outs)),
+             "constexpr bool HEAVY = %s;   // one element per lane (8-byte accesses) on every batch: chains with an inversion, as the library's k_unary_heavy" % ("true" if (ept or self.default_ept()) == 1 else "false"),
+             "constexpr int NSEL = %d;" % self.nsel,
+             "struct Args { const spint* in[NIN]; spint* out[NOUT]; const int* sel[NSEL > 0 ? NSEL : 1]; };", "",
+             "// the chain on one element's registers; F = Field<P, FAST>",
+             "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i < self.nin else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)])]
+        L += self._body_lines()
         L += ["}", "",
               "template <int EPT>", "__global__ __launch_bounds__(BLOCK) %svoid k_chain(Args A, size_t nthreads, Ld L) {" % ("__attribute__((amdgpu_waves_per_eu(%d, %d))) " % (waves, waves) if waves else "")]
         votel = ["bool fast = %s;" % ("true" if policy == "fast" else "false"),
@@ -285,6 +400,8 @@ class Chain:
 
     @property
     def aos_symbol(self) -> str:
+        if self.wl == 32:
+            raise ValueError("the element-major entry is not built at word length 32: convert with modarith_amd_w32_aos_to_soa and call %s" % self.symbol)
         return "chain_%s_%s_aos" % (self.name, self.prime)
 
     def _aos_kernel(self, votel: List[str]) -> List[str]:
@@ -414,14 +531,15 @@ class Chain:
 
     # ------------------------------------------------------------------ building the plug-in
     def lib_path(self, plugin_dir: Optional[str] = None) -> str:
-        return os.path.join(plugin_dir or _gen.PLUGIN_DIR, "libmodarith_amd_chain_%s_%s.so" % (self.name, self.prime))
+        return os.path.join(plugin_dir or _gen.PLUGIN_DIR, "libmodarith_amd_chain_%s_%s.so" % (self.name, self._tag))
 
-    def build(self, plugin_dir: Optional[str] = None, force: bool = False, verbose: bool = False, ept: Optional[int] = None, policy: str = "vote", waves: int = 0) -> "FusedChain":
+    def build(self, plugin_dir: Optional[str] = None, force: bool = False, verbose: bool = False, ept: Optional[int] = None, policy: str = "vote", waves: int = 0,
+              block: Optional[int] = None) -> "FusedChain":
         from .build import ARCH, FLAGS, HIPCC, _stamp
         d = plugin_dir or _gen.PLUGIN_DIR
         os.makedirs(d, exist_ok=True)
-        src_text = self.source(ept, policy, waves)
-        base = "chain_%s_%s" % (self.name, self.prime)
+        src_text = self.source(ept, policy, waves, block)
+        base = "chain_%s_%s" % (self.name, self._tag)
         src, obj, meta = (os.path.join(d, base + e) for e in (".hip", ".o", ".json"))
         lib = self.lib_path(d)
         key = hashlib.sha256((" ".join(FLAGS) + "\n" + src_text + "\n" + emit.header_text(self.params) + "\n" + _stamp()).encode()).hexdigest()
@@ -443,7 +561,7 @@ class Chain:
             subprocess.check_call([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib + tmp, obj + tmp, "-L", HERE, "-l:libmodarith_amd.so",
                                    "-Wl,-rpath,$ORIGIN/" + os.path.relpath(HERE, d), "-Wl,-rpath," + HERE])
             with open(meta + tmp, "w") as f:
-                json.dump({"chain": self.name, "prime": self.prime, "inputs": self.nin, "selectors": self.nsel, "outputs": len(self.outs),
+                json.dump({"chain": self.name, "prime": self.prime, "wl": self.wl, "inputs": self.nin, "selectors": self.nsel, "outputs": len(self.outs),
                            "ops": [o[0] for o in self.ops], "symbol": self.symbol, "hash": key}, f, indent=1)
             os.replace(obj + tmp, obj)
             os.replace(lib + tmp, lib)
@@ -452,7 +570,8 @@ class Chain:
 
 
 class FusedChain:
-    """a built chain: call it with one device batch per input (flat [N, n] or tiled [n / tile, N, tile], all the same shape)"""
+    """a built chain: call it with one device batch per input (flat [N, n] or tiled [n / tile, N, tile], all the same shape; int64
+    limbs, or int32 for a chain of the 32-bit word form)"""
     def __init__(self, chain: Chain, lib: str, built: bool):
         self.chain, self.path, self.built = chain, lib, built
         _lib.load()
@@ -468,6 +587,8 @@ class FusedChain:
         import torch
         ch = self.chain
         N = ch.params.nlimbs
+        if ch.wl == 32:
+            raise ValueError("the element-major entry is not built at word length 32: convert with modarith_amd_w32_aos_to_soa and call %s" % ch.symbol)
         if len(inputs) != ch.nin + ch.nsel:
             raise ValueError("chain %s takes %d element arrays followed by %d int32 selector arrays" % (ch.name, ch.nin, ch.nsel))
         elems, sels = inputs[:ch.nin], inputs[ch.nin:]
@@ -498,7 +619,7 @@ class FusedChain:
         dev = device if device is not None else inputs[0].device
         F = self._fields.get(dev)
         if F is None:                                  # binding a Field derives the prime's constants: once per device, not per call
-            F = self._fields[dev] = Field(ch.prime, dev)
+            F = self._fields[dev] = Field(ch.prime, dev, wl=ch.wl)
         outs = list(out) if out is not None else [F._out(inputs[0], None) for _ in ch.outs]
         if len(outs) != len(ch.outs):
             raise ValueError("chain %s has %d outputs" % (ch.name, len(ch.outs)))
@@ -523,13 +644,14 @@ def bench_chain(prime: str = "X25519") -> Chain:
 
 # ---------------------------------------------------------------------------------------------------------------------
 # command line: a chain written as text, for consumers that do not otherwise touch Python
+#   python -m modarith_amd.fuse 32 X25519 accept "..."        (the same chain over the 32-bit word form)
 #   python -m modarith_amd.fuse X25519 accept "in x, y; t = modadd(x, y); w = modsub(x, y); s = modsqr(modmul(t, w)); out modinv(s)"
-def parse(prime: str, name: str, text: str) -> Chain:
+def parse(prime: str, name: str, text: str, wl: int = 64) -> Chain:
     """statements separated by ';':  `in a, b`  (element inputs, in order) | `sel d` (int32 selector inputs) | `v = f(args)` |
     `g2, f2 = modcsw(d, g, f)` | `out expr, ...`.  Expressions nest: modsqr(modmul(a, b)).  Integers are accepted where the
     function takes one (modmli, modnsqr).  Function names are the chain's methods, i.e. field.c's."""
     import ast
-    ch = Chain(prime, name)
+    ch = Chain(prime, name, wl)
     env = {}
 
     def ev(node):
@@ -577,11 +699,14 @@ def parse(prime: str, name: str, text: str) -> Chain:
 
 def main(argv: List[str]) -> int:
     args = [a for a in argv if not a.startswith("--")]
+    wl = 64
+    if len(args) == 4 and args[0] in ("32", "64"):      # the word length first, as the reference's generators take it
+        wl, args = int(args[0]), args[1:]
     if len(args) != 3:
-        print('usage: python -m modarith_amd.fuse <prime or tag> <name> "in a, b; t = modadd(a, b); out modsqr(t)" [--force] [--source]')
+        print('usage: python -m modarith_amd.fuse [32] <prime or tag> <name> "in a, b; t = modadd(a, b); out modsqr(t)" [--force] [--source]')
         return 2
     try:
-        ch = parse(*args)
+        ch = parse(*args, wl=wl)
         if "--source" in argv:
             print(ch.source())
             return 0
@@ -592,7 +717,8 @@ def main(argv: List[str]) -> int:
     print("%s %s" % ("built" if f.built else "up to date:", f.path))
     print("int %s(const void *const *in /* %d element batches%s */, void *const *out /* %d */, size_t n, size_t ld, void *stream);"
           % (ch.symbol, ch.nin, (", then %d int32 selector arrays" % ch.nsel) if ch.nsel else "", len(ch.outs)))
-    print("int %s(const void *const *in, void *const *out, size_t n, void *stream);   /* the same over element-major arrays x[n][Nlimbs] */" % ch.aos_symbol)
+    if ch.wl == 64:
+        print("int %s(const void *const *in, void *const *out, size_t n, void *stream);   /* the same over element-major arrays x[n][Nlimbs] */" % ch.aos_symbol)
     print("HBM bytes per element: %d fused, %d call by call" % (ch.traffic_bytes(), ch.unfused_traffic_bytes()))
     return 0
 

@@ -343,3 +343,20 @@ def derive(name: str, family: Optional[str] = None, radix: Optional[int] = None,
     if radix is None and fam == "monty" and wl == 64:
         radix = RADIX_64.get(name)
     return derive_pseudo(name, p, radix, wl) if fam == "pseudo" else derive_monty(name, p, radix, wl)
+
+
+def w32_inv_in_contract(fp: FieldParams, limbs):
+    """The in-contract predicate of the 32-bit simultaneous inversion (csrc/kernels32.h inv_in_contract, where it is justified): digit
+    form below 2^(Nbits+1) -- limbs 0..N-2 below 2^Radix, top limb below 2^(Nbits + 1 - Radix (N-1)).  Elements that pass share an
+    inversion with their neighbours in modinv_<P>_w32_batch; the others get one of their own.  Every element below 2p in digit form
+    passes.  `limbs`: one element (N unsigned limbs) -> bool, or a limb-major batch [N, n] -> one bool per element."""
+    import numpy as np
+    if fp.wl != 32:
+        raise ValueError("the predicate belongs to the 32-bit word form")
+    N, R = fp.nlimbs, fp.radix
+    topb = fp.n + 1 - R * (N - 1)
+    a = np.asarray(limbs, dtype=np.uint64)
+    if a.shape[0] != N:
+        raise ValueError("expected %d limbs" % N)
+    ok = ((a[:N - 1] >> np.uint64(R)) == 0).all(axis=0) & ((a[N - 1] >> np.uint64(topb)) == 0)
+    return bool(ok) if a.ndim == 1 else ok
