@@ -1,6 +1,8 @@
 // modarith_amd/csrc/capi_prime.inc -- per-prime body of the C-ABI shim.  Included by capi_<PRIME>.hip
 // with MA_P (parameter struct), MA_NAME (token) defined, and optionally MA_LADDER_A24 / MA_LADDER_COF.
-// Every entry point declared by MODARITH_AMD_DECLARE(P) in include/modarith_amd.h is defined here.
+// Every entry point declared by MODARITH_AMD_DECLARE(P) in include/modarith_amd.h is defined here or in capi_field.inc, the part
+// shared with the 32-bit word form (capi_w32.inc): this file keeps the product-policy dispatch, modmuls, the lazy forms, the time.c
+// protocol and the ladders.
 #include "../../include/modarith_amd.h"
 #include "capi_common.h"
 #include "kernels.h"
@@ -12,6 +14,7 @@
 #include "fe28.h"
 #endif
 #include <string.h>
+#include <algorithm>
 
 #define MA_CAT3_(a, b, c) a##_##b##_##c
 #define MA_CAT3(a, b, c) MA_CAT3_(a, b, c)
@@ -23,77 +26,22 @@ using namespace ma;
 using P = MA_P;
 constexpr int NL = P::N;
 constexpr int NB = P::NBYTES;
-constexpr size_t INV_SIMUL_LANES = 16384;      // simultaneous inversion: lanes kept busy before elements start sharing an inversion
-constexpr size_t INV_SIMUL_MIN = 32768;        // batches from this size on share inversions
+#define MA_WHAT(fn) fn
+#define MA_WHAT2(fn, how) fn "(" how ")"
+// streaming kernels: 16 bytes per lane at the most, workgroups of BLOCK
+int ept_cap() { return 2; }
+int stream_block() { return BLOCK; }
+constexpr bool INV_SIMUL = NL <= 9 && P::RADIX <= 60;   // (wider fields keep one inversion per element: register footprint; radix > 60: no flag bits)
+}  // namespace
+#include "capi_field.inc"
 
-// The limb stride argument of every batched entry point (include/modarith_amd.h): ld >= n is the flat layout, ld < n the tiled
-// one (tiles of ld elements, ld a power of two >= 128) -> kernels.h Ld.  false (and the error text) for an unusable stride.
-bool make_ld(size_t n, size_t ld, Ld* L, const char* what) {
-    if (ld >= n) { *L = Ld(ld); return true; }
-    if (ld < 128 || (ld & (ld - 1)) != 0) {
-        set_error(std::string(what) + ": a limb stride below n selects the tiled layout and must be a power of two >= 128");
-        return false;
-    }
-    *L = Ld(ld, (unsigned)__builtin_ctzll((unsigned long long)ld));
-    return true;
+namespace {
+int modinv_each(const spint* x, spint* z, size_t n, size_t ld, void* st) {
+    if (force_fast() && P::SPLIT > 0) return launch_unary_heavy<OpInv<P, true>>(x, z, n, ld, st, "modinv(fast)");
+    if (force_exact() || P::SPLIT == 0) return launch_unary_heavy<OpInv<P>>(x, z, n, ld, st, "modinv(exact)");
+    return launch_unary_heavy<OpAutoUnary<P, OpInv>>(x, z, n, ld, st, "modinv");
 }
-#define GRID(x) grid_for((x), BLOCK, L.s != 63)       /* launch geometry of a streaming kernel over the batch described by L */
-#define MA_LD(what)                                                  \
-    Ld L;                                                            \
-    if (!make_ld(n, ld, &L, what)) return (int)hipErrorInvalidValue;
-
-template <class Op>
-int launch_binary(const spint* a, const spint* b, spint* c, size_t n, size_t ld, void* stream, const char* what) {
-    if (n == 0) return 0;
-    MA_LD(what)
-    hipStream_t s = (hipStream_t)stream;
-    if (n >= 2 && ld % 2 == 0 && aligned16(a) && aligned16(b) && aligned16(c)) {
-        size_t nt = n / 2;
-        k_binary<P, Op, 2><<<GRID(nt), BLOCK, 0, s>>>(a, b, c, nt, L, L, L);
-        const size_t o = L.off<NL>(n - 1);               // the odd element out: one lane on the 8-byte path, at its own address
-        if (n & 1) k_binary<P, typename ScalarOp<Op>::type, 1><<<1, BLOCK, 0, s>>>(a + o, b + o, c + o, 1, Ld(L.ld), Ld(L.ld), Ld(L.ld));
-    } else {
-        k_binary<P, typename ScalarOp<Op>::type, 1><<<GRID(n), BLOCK, 0, s>>>(a, b, c, n, L, L, L);
-    }
-    return check_launch(what);
-}
-
-template <class Op>
-int launch_unary(const spint* a, spint* c, size_t n, size_t ld, void* stream, const char* what) {
-    if (n == 0) return 0;
-    MA_LD(what)
-    hipStream_t s = (hipStream_t)stream;
-    if (n >= 2 && ld % 2 == 0 && aligned16(a) && aligned16(c)) {
-        size_t nt = n / 2;
-        k_unary<P, Op, 2><<<GRID(nt), BLOCK, 0, s>>>(a, c, nt, L, L);
-        const size_t o = L.off<NL>(n - 1);
-        if (n & 1) k_unary<P, typename ScalarOp<Op>::type, 1><<<1, BLOCK, 0, s>>>(a + o, c + o, 1, Ld(L.ld), Ld(L.ld));
-    } else {
-        k_unary<P, typename ScalarOp<Op>::type, 1><<<GRID(n), BLOCK, 0, s>>>(a, c, n, L, L);
-    }
-    return check_launch(what);
-}
-
-// long-running per-element kernels (inversion): one element per lane, small workgroups
-template <class Op>
-int launch_unary_heavy(const spint* a, spint* c, size_t n, size_t ld, void* stream, const char* what) {
-    if (n == 0) return 0;
-    MA_LD(what)
-    k_unary_heavy<P, Op><<<GRID(n), BLOCK, 0, (hipStream_t)stream>>>(a, c, n, L, L);
-    return check_launch(what);
-}
-
-// ---- scalar staging: run a batched call on one element held in host memory
-struct Stage : StageBase {
-    template <class T>
-    T* put(const T* host, size_t count) {
-        T* d = reinterpret_cast<T*>(take(count * sizeof(T)));
-        if (host) h2d(d, host, count * sizeof(T));
-        return d;
-    }
-    template <class T>
-    void get(T* host, const T* dev, size_t count) { d2h(host, dev, count * sizeof(T)); }
-};
+bool inv_may_share() { return !force_exact(); }
 template <int EPT, bool AUTO>
 void launch_shared(const spint* a, const Elem<P>& b0, spint* c, size_t nt, Ld L, unsigned grid, hipStream_t s) {
     k_mul_shared<P, EPT, AUTO><<<grid, BLOCK, 0, s>>>(a, b0, c, nt, L, L);
@@ -102,10 +50,7 @@ void launch_shared(const spint* a, const Elem<P>& b0, spint* c, size_t nt, Ld L,
 
 extern "C" {
 
-// ------------------------------------------------------------------ batched form
-int BATCH(modadd)(const ma_spint* a, const ma_spint* b, ma_spint* c, size_t n, size_t ld, void* st) { return launch_binary<OpAdd<P>>(a, b, c, n, ld, st, "modadd"); }
-int BATCH(modsub)(const ma_spint* a, const ma_spint* b, ma_spint* c, size_t n, size_t ld, void* st) { return launch_binary<OpSub<P>>(a, b, c, n, ld, st, "modsub"); }
-int BATCH(modneg)(const ma_spint* b, ma_spint* c, size_t n, size_t ld, void* st) { return launch_unary<OpNeg<P>>(b, c, n, ld, st, "modneg"); }
+// ------------------------------------------------------------------ batched form: what chooses a product policy, and what only this word length has
 int BATCH(modadd_lazy)(const ma_spint* a, const ma_spint* b, ma_spint* c, size_t n, size_t ld, void* st) { return launch_binary<OpAddLazy<P>>(a, b, c, n, ld, st, "modadd_lazy"); }
 int BATCH(modsub_lazy)(const ma_spint* a, const ma_spint* b, ma_spint* c, size_t n, size_t ld, void* st) { return launch_binary<OpSubLazy<P>>(a, b, c, n, ld, st, "modsub_lazy"); }
 int BATCH(modneg_lazy)(const ma_spint* b, ma_spint* c, size_t n, size_t ld, void* st) { return launch_unary<OpNegLazy<P>>(b, c, n, ld, st, "modneg_lazy"); }
@@ -123,7 +68,6 @@ int BATCH(modsqr)(const ma_spint* a, ma_spint* c, size_t n, size_t ld, void* st)
     if (force_exact() || P::SPLIT == 0) return launch_unary<OpSqr<P>>(a, c, n, ld, st, "modsqr(exact)");
     return launch_unary<OpSqrAuto<P>>(a, c, n, ld, st, "modsqr");
 }
-int BATCH(modcpy)(const ma_spint* a, ma_spint* c, size_t n, size_t ld, void* st) { return launch_unary<OpCpy<P>>(a, c, n, ld, st, "modcpy"); }
 int BATCH(nres)(const ma_spint* a, ma_spint* c, size_t n, size_t ld, void* st) {
     if (force_fast() && P::SPLIT > 0) return launch_unary<OpNres<P, true>>(a, c, n, ld, st, "nres(fast)");
     if (force_exact() || P::SPLIT == 0 || !P::MONTGOMERY) return launch_unary<OpNres<P>>(a, c, n, ld, st, "nres(exact)");
@@ -137,45 +81,6 @@ int BATCH(redc)(const ma_spint* a, ma_spint* c, size_t n, size_t ld, void* st) {
 int BATCH(modpro)(const ma_spint* a, ma_spint* c, size_t n, size_t ld, void* st) {
     if (force_exact() || P::SPLIT == 0) return launch_unary_heavy<OpPro<P>>(a, c, n, ld, st, "modpro(exact)");
     return launch_unary_heavy<OpAutoUnary<P, OpPro>>(a, c, n, ld, st, "modpro");
-}
-
-int BATCH(modinv)(const ma_spint* x, const ma_spint* h, ma_spint* z, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("modinv")
-    // Large batches without a caller-supplied progenitor: simultaneous inversion (kernels.h k_inv_simul), one modinv per up to
-    // 64 elements.  The prefix products go to the output buffer, or -- when the output IS the input -- to stream-ordered
-    // scratch of the library's own (not during stream capture).  MA_INV_SIMUL=0 keeps one modinv per element.  Same words
-    // either way (normalised outputs).
-    if constexpr (NL <= 9 && P::RADIX <= 60)        // (wider fields keep one inversion per element: register footprint; radix > 60: no flag bits)
-    if (h == nullptr && n >= INV_SIMUL_MIN && inv_simul() && !force_exact()) {
-        hipStream_t s = (hipStream_t)st;
-        // elements per inversion: up to 64, fewer only for batches too small to leave 16 384 lanes busy (measured at 2^22
-        // elements: 64 per inversion on 65 536 lanes 1.17e10/s, 32 per inversion on 131 072 lanes 1.11e10/s)
-        size_t rounds = (n + INV_SIMUL_LANES - 1) / INV_SIMUL_LANES;
-        if (rounds > 64) rounds = 64;
-        const size_t lanes = (n + rounds - 1) / rounds;
-        const unsigned grid = (unsigned)((lanes + BLOCK - 1) / BLOCK);
-        if (x != z) {
-            k_inv_simul<P><<<grid, BLOCK, 0, s>>>(x, z, z, n, lanes, (int)rounds, L, L, L);
-            return check_launch("modinv(simultaneous)");
-        }
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (s == nullptr || (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone)) {
-            if (spint* ws = static_cast<spint*>(scratch_alloc(n * NL * sizeof(spint), s))) {
-                k_inv_simul<P><<<grid, BLOCK, 0, s>>>(x, z, ws, n, lanes, (int)rounds, L, L, Ld(n));
-                scratch_free(ws, s);
-                return check_launch("modinv(simultaneous, in place)");
-            }
-        }
-        (void)hipGetLastError();
-    }
-    if (h == nullptr) {
-        if (force_fast() && P::SPLIT > 0) return launch_unary_heavy<OpInv<P, true>>(x, z, n, ld, st, "modinv(fast)");
-        if (force_exact() || P::SPLIT == 0) return launch_unary_heavy<OpInv<P>>(x, z, n, ld, st, "modinv(exact)");
-        return launch_unary_heavy<OpAutoUnary<P, OpInv>>(x, z, n, ld, st, "modinv");
-    }
-    k_inv_h<P><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(x, h, z, n, L, L, L);
-    return check_launch("modinv(h)");
 }
 
 int BATCH(modsqrt)(const ma_spint* x, const ma_spint* h, ma_spint* r, size_t n, size_t ld, void* st) {
@@ -220,123 +125,6 @@ int BATCH(modmuls)(const ma_spint* a, const ma_spint* b0_host, ma_spint* c, size
     return check_launch("modmuls");
 }
 
-int BATCH(modmli)(const ma_spint* a, int b, ma_spint* c, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("modmli")
-    hipStream_t s = (hipStream_t)st;
-    if (n >= 2 && ld % 2 == 0 && aligned16(a) && aligned16(c)) {
-        size_t nt = n / 2;
-        k_mli<P, 2><<<GRID(nt), BLOCK, 0, s>>>(a, b, c, nt, L, L);
-        const size_t o = L.off<NL>(n - 1);
-        if (n & 1) k_mli<P, 1><<<1, BLOCK, 0, s>>>(a + o, b, c + o, 1, Ld(L.ld), Ld(L.ld));
-    } else {
-        k_mli<P, 1><<<GRID(n), BLOCK, 0, s>>>(a, b, c, n, L, L);
-    }
-    return check_launch("modmli");
-}
-
-int BATCH(modnsqr)(ma_spint* a, int k, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("modnsqr")
-    k_nsqr<P><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(a, k, n, L);
-    return check_launch("modnsqr");
-}
-
-#define MA_INPLACE(fn, KIND, HAS_OUT)                                                                  \
-    int BATCH(fn)(ma_spint * a, int* out, size_t n, size_t ld, void* st) {                             \
-        if (n == 0) return 0;                                                                          \
-        MA_LD(#fn)                                                                                     \
-        k_inplace<P, KIND><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(a, out, n, L);                 \
-        return check_launch(#fn);                                                                      \
-    }
-MA_INPLACE(modfsb, K_MODFSB, 1)
-MA_INPLACE(flatten, K_FLATTEN, 1)
-MA_INPLACE(prop, K_PROP, 1)        /* flag[j] = -1 where the top limb went negative (the mask prop returns), else 0 */
-int BATCH(modhaf)(ma_spint* a, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("modhaf")
-    k_inplace<P, K_MODHAF><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(a, nullptr, n, L);
-    return check_launch("modhaf");
-}
-#define MA_PRED(fn, KIND)                                                                              \
-    int BATCH(fn)(const ma_spint* a, int* out, size_t n, size_t ld, void* st) {                        \
-        if (n == 0) return 0;                                                                          \
-        MA_LD(#fn)                                                                                     \
-        k_inplace<P, KIND><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(const_cast<ma_spint*>(a), out, n, L); \
-        return check_launch(#fn);                                                                      \
-    }
-MA_PRED(modis1, K_MODIS1)
-MA_PRED(modis0, K_MODIS0)
-MA_PRED(modsign, K_MODSIGN)
-MA_PRED(modlimbs, K_MODLIMBS)
-int BATCH(modcmp)(const ma_spint* a, const ma_spint* b, int* out, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("modcmp")
-    k_cmp<P><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(a, b, out, n, L, L);
-    return check_launch("modcmp");
-}
-int BATCH(modshl)(unsigned int k, ma_spint* a, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("modshl")
-    k_shift<P, true><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(k, a, nullptr, n, L);
-    return check_launch("modshl");
-}
-int BATCH(modshr)(unsigned int k, ma_spint* a, int* out, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("modshr")
-    k_shift<P, false><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(k, a, out, n, L);
-    return check_launch("modshr");
-}
-int BATCH(modint)(int x, ma_spint* a, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("modint")
-    k_fill<P, K_INT><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(x, a, n, L);
-    return check_launch("modint");
-}
-int BATCH(modzer)(ma_spint* a, size_t n, size_t ld, void* st) { return BATCH(modint)(0, a, n, ld, st); }
-int BATCH(modone)(ma_spint* a, size_t n, size_t ld, void* st) { return BATCH(modint)(1, a, n, ld, st); }
-int BATCH(mod2r)(unsigned int r, ma_spint* a, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("mod2r")
-    k_fill<P, K_2R><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>((int)r, a, n, L);
-    return check_launch("mod2r");
-}
-int BATCH(modcmv)(const int* d, const ma_spint* g, ma_spint* f, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("modcmv")
-    k_cond<P, false><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(d, const_cast<ma_spint*>(g), f, n, L, L);
-    return check_launch("modcmv");
-}
-int BATCH(modcsw)(const int* d, ma_spint* g, ma_spint* f, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("modcsw")
-    k_cond<P, true><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(d, g, f, n, L, L);
-    return check_launch("modcsw");
-}
-int BATCH(modimp)(const char* b, ma_spint* a, int* flag, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("modimp")
-    if (NB % 8 == 0 && (reinterpret_cast<uintptr_t>(b) & 7u)) { set_error("modimp: byte records must be 8-byte aligned"); return (int)hipErrorInvalidValue; }
-    k_imp<P><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(reinterpret_cast<const unsigned char*>(b), a, flag, n, L);
-    return check_launch("modimp");
-}
-int BATCH(modexp)(const ma_spint* a, char* b, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("modexp")
-    if (NB % 8 == 0 && (reinterpret_cast<uintptr_t>(b) & 7u)) { set_error("modexp: byte records must be 8-byte aligned"); return (int)hipErrorInvalidValue; }
-    k_exp<P><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(a, reinterpret_cast<unsigned char*>(b), n, L);
-    return check_launch("modexp");
-}
-
-// synthetic inputs (kernels.h k_uniform): out[j] = canonical limbs of the (seed, array, first + j) element, uniform mod p
-int BATCH(moduniform)(unsigned long long seed, unsigned long long array, size_t first, int plus_p, ma_spint* out, size_t n, size_t ld, void* st) {
-    if (n == 0) return 0;
-    MA_LD("moduniform")
-    const spint s0 = (spint)seed * 0x9E3779B97F4A7C15ull + (spint)array * 0xD1342543DE82EF95ull;
-    k_uniform<P><<<GRID(n), BLOCK, 0, (hipStream_t)st>>>(s0, first, plus_p, out, n, L);
-    return check_launch("moduniform");
-}
-
 // time.c protocol on the device: z[j] = redc(chain(x[j], y[j])); kind 0 modmul, 1 modsqr, 2 modinv
 int BATCH(time_protocol)(int kind, const ma_spint* x, const ma_spint* y, ma_spint* z, long outer, size_t n, size_t ld, void* st) {
     if (n == 0) return 0;
@@ -351,182 +139,6 @@ int BATCH(time_protocol)(int kind, const ma_spint* x, const ma_spint* y, ma_spin
     else { if (kind == 0) MA_TIME_LAUNCH(0, 2); else if (kind == 1) MA_TIME_LAUNCH(1, 2); else MA_TIME_LAUNCH(2, 2); }
 #undef MA_TIME_LAUNCH
     return check_launch("time_protocol");
-}
-
-// ------------------------------------------------------------------ scalar form (n = 1 through the device)
-#define MA_SC_BIN(fn)                                                                         \
-    void SCALAR(fn)(const ma_spint* a, const ma_spint* b, ma_spint* c) {                      \
-        Stage s;                                                                              \
-        spint *da = s.put(a, NL), *db = s.put(b, NL), *dc = s.put<spint>(nullptr, NL);        \
-        if (!s.bad) s.check(BATCH(fn)(da, db, dc, 1, 1, nullptr), #fn);                                 \
-        s.get(c, dc, NL);                                                                     \
-    }
-#define MA_SC_UN(fn)                                                                          \
-    void SCALAR(fn)(const ma_spint* a, ma_spint* c) {                                         \
-        Stage s;                                                                              \
-        spint *da = s.put(a, NL), *dc = s.put<spint>(nullptr, NL);                            \
-        if (!s.bad) s.check(BATCH(fn)(da, dc, 1, 1, nullptr), #fn);                                     \
-        s.get(c, dc, NL);                                                                     \
-    }
-MA_SC_BIN(modadd)
-MA_SC_BIN(modsub)
-MA_SC_BIN(modmul)
-MA_SC_UN(modneg)
-MA_SC_UN(modsqr)
-MA_SC_UN(modcpy)
-MA_SC_UN(modpro)
-MA_SC_UN(nres)
-MA_SC_UN(redc)
-
-void SCALAR(modmli)(const ma_spint* a, int b, ma_spint* c) {
-    Stage s;
-    spint *da = s.put(a, NL), *dc = s.put<spint>(nullptr, NL);
-    if (!s.bad) s.check(BATCH(modmli)(da, b, dc, 1, 1, nullptr), "modmli");
-    s.get(c, dc, NL);
-}
-void SCALAR(modnsqr)(ma_spint* a, int n) {
-    Stage s;
-    spint* da = s.put(a, NL);
-    if (!s.bad) s.check(BATCH(modnsqr)(da, n, 1, 1, nullptr), "modnsqr");
-    s.get(a, da, NL);
-}
-void SCALAR(modinv)(const ma_spint* x, const ma_spint* h, ma_spint* z) {
-    Stage s;
-    spint *dx = s.put(x, NL), *dh = h ? s.put(h, NL) : nullptr, *dz = s.put<spint>(nullptr, NL);
-    if (!s.bad) s.check(BATCH(modinv)(dx, dh, dz, 1, 1, nullptr), "modinv");
-    s.get(z, dz, NL);
-}
-void SCALAR(modsqrt)(const ma_spint* x, const ma_spint* h, ma_spint* r) {
-    Stage s;
-    spint *dx = s.put(x, NL), *dh = h ? s.put(h, NL) : nullptr, *dr = s.put<spint>(nullptr, NL);
-    if (!s.bad) s.check(BATCH(modsqrt)(dx, dh, dr, 1, 1, nullptr), "modsqrt");
-    s.get(r, dr, NL);
-}
-int SCALAR(modqr)(const ma_spint* h, const ma_spint* x) {
-    Stage s;
-    spint *dx = s.put(x, NL), *dh = h ? s.put(h, NL) : nullptr;
-    int* dr = s.put<int>(nullptr, 1);
-    if (!s.bad) s.check(BATCH(modqr)(dh, dx, dr, 1, 1, nullptr), "modqr");
-    int r;
-    s.get(&r, dr, 1);
-    return s.answer(r);
-}
-#define MA_SC_INPLACE_RET(fn, rtype)                                                          \
-    rtype SCALAR(fn)(ma_spint* a) {                                                           \
-        Stage s;                                                                              \
-        spint* da = s.put(a, NL);                                                             \
-        int* dr = s.put<int>(nullptr, 1);                                                     \
-        if (!s.bad) s.check(BATCH(fn)(da, dr, 1, 1, nullptr), #fn);                                     \
-        int r;                                                                                \
-        s.get(&r, dr, 1);                                                                     \
-        s.get(a, da, NL);                                                                     \
-        return (rtype)r;                                                                      \
-    }
-MA_SC_INPLACE_RET(modfsb, ma_spint)
-MA_SC_INPLACE_RET(flatten, ma_spint)
-MA_SC_INPLACE_RET(prop, ma_spint)   /* (ma_spint)(int)-1 = all ones, as pseudo.py:251 returns */
-#define MA_SC_PRED(fn)                                                                        \
-    int SCALAR(fn)(const ma_spint* a) {                                                       \
-        Stage s;                                                                              \
-        spint* da = s.put(a, NL);                                                             \
-        int* dr = s.put<int>(nullptr, 1);                                                     \
-        if (!s.bad) s.check(BATCH(fn)(da, dr, 1, 1, nullptr), #fn);                                     \
-        int r;                                                                                \
-        s.get(&r, dr, 1);                                                                     \
-        return s.answer(r);                                                                   \
-    }
-MA_SC_PRED(modis1)
-MA_SC_PRED(modis0)
-MA_SC_PRED(modsign)
-int SCALAR(modcmp)(const ma_spint* a, const ma_spint* b) {
-    Stage s;
-    spint *da = s.put(a, NL), *db = s.put(b, NL);
-    int* dr = s.put<int>(nullptr, 1);
-    if (!s.bad) s.check(BATCH(modcmp)(da, db, dr, 1, 1, nullptr), "modcmp");
-    int r;
-    s.get(&r, dr, 1);
-    return s.answer(r);
-}
-void SCALAR(modzer)(ma_spint* a) {
-    Stage s;
-    spint* da = s.put<spint>(nullptr, NL);
-    if (!s.bad) s.check(BATCH(modzer)(da, 1, 1, nullptr), "modzer");
-    s.get(a, da, NL);
-}
-void SCALAR(modone)(ma_spint* a) {
-    Stage s;
-    spint* da = s.put<spint>(nullptr, NL);
-    if (!s.bad) s.check(BATCH(modone)(da, 1, 1, nullptr), "modone");
-    s.get(a, da, NL);
-}
-void SCALAR(modint)(int x, ma_spint* a) {
-    Stage s;
-    spint* da = s.put<spint>(nullptr, NL);
-    if (!s.bad) s.check(BATCH(modint)(x, da, 1, 1, nullptr), "modint");
-    s.get(a, da, NL);
-}
-void SCALAR(mod2r)(unsigned int r, ma_spint* a) {
-    Stage s;
-    spint* da = s.put<spint>(nullptr, NL);
-    if (!s.bad) s.check(BATCH(mod2r)(r, da, 1, 1, nullptr), "mod2r");
-    s.get(a, da, NL);
-}
-void SCALAR(modcmv)(int b, const ma_spint* g, volatile ma_spint* f) {
-    Stage s;
-    int bb = b;
-    int* dd = s.put(&bb, 1);
-    spint *dg = s.put(g, NL), *df = s.put(const_cast<const ma_spint*>(f), NL);
-    if (!s.bad) s.check(BATCH(modcmv)(dd, dg, df, 1, 1, nullptr), "modcmv");
-    s.get(const_cast<ma_spint*>(f), df, NL);
-}
-void SCALAR(modcsw)(int b, volatile ma_spint* g, volatile ma_spint* f) {
-    Stage s;
-    int bb = b;
-    int* dd = s.put(&bb, 1);
-    spint *dg = s.put(const_cast<const ma_spint*>(g), NL), *df = s.put(const_cast<const ma_spint*>(f), NL);
-    if (!s.bad) s.check(BATCH(modcsw)(dd, dg, df, 1, 1, nullptr), "modcsw");
-    s.get(const_cast<ma_spint*>(g), dg, NL);
-    s.get(const_cast<ma_spint*>(f), df, NL);
-}
-void SCALAR(modshl)(unsigned int n, ma_spint* a) {
-    Stage s;
-    spint* da = s.put(a, NL);
-    if (!s.bad) s.check(BATCH(modshl)(n, da, 1, 1, nullptr), "modshl");
-    s.get(a, da, NL);
-}
-int SCALAR(modshr)(unsigned int n, ma_spint* a) {
-    Stage s;
-    spint* da = s.put(a, NL);
-    int* dr = s.put<int>(nullptr, 1);
-    if (!s.bad) s.check(BATCH(modshr)(n, da, dr, 1, 1, nullptr), "modshr");
-    int r;
-    s.get(&r, dr, 1);
-    s.get(a, da, NL);
-    return r;
-}
-void SCALAR(modhaf)(ma_spint* a) {
-    Stage s;
-    spint* da = s.put(a, NL);
-    if (!s.bad) s.check(BATCH(modhaf)(da, 1, 1, nullptr), "modhaf");
-    s.get(a, da, NL);
-}
-void SCALAR(modexp)(const ma_spint* a, char* b) {
-    Stage s;
-    spint* da = s.put(a, NL);
-    char* db = s.put<char>(nullptr, NB);
-    if (!s.bad) s.check(BATCH(modexp)(da, db, 1, 1, nullptr), "modexp");
-    s.get(b, db, NB);
-}
-int SCALAR(modimp)(const char* b, ma_spint* a) {
-    Stage s;
-    char* db = s.put(b, NB);
-    spint* da = s.put<spint>(nullptr, NL);
-    int* dr = s.put<int>(nullptr, 1);
-    if (!s.bad) s.check(BATCH(modimp)(db, da, dr, 1, 1, nullptr), "modimp");
-    int r;
-    s.get(&r, dr, 1);
-    s.get(a, da, NL);
-    return s.answer(r);
 }
 
 // ------------------------------------------------------------------ RFC 7748 ladder

@@ -346,7 +346,7 @@ def derive(name: str, family: Optional[str] = None, radix: Optional[int] = None,
 
 
 def w32_inv_in_contract(fp: FieldParams, limbs):
-    """The in-contract predicate of the 32-bit simultaneous inversion (csrc/kernels32.h inv_in_contract, where it is justified): digit
+    """The in-contract predicate of the 32-bit simultaneous inversion (csrc/kernels.h inv_in_contract, where it is justified): digit
     form below 2^(Nbits+1) -- limbs 0..N-2 below 2^Radix, top limb below 2^(Nbits + 1 - Radix (N-1)).  Elements that pass share an
     inversion with their neighbours in modinv_<P>_w32_batch; the others get one of their own.  Every element below 2p in digit form
     passes.  `limbs`: one element (N unsigned limbs) -> bool, or a limb-major batch [N, n] -> one bool per element."""

@@ -1,4 +1,4 @@
-"""The classifier of tools/ct_audit.py over the 32-bit modcsw / modcmv kernels (ma32::k_cond of csrc/kernels32.h, in the three
+"""The classifier of tools/ct_audit.py over the 32-bit modcsw / modcmv kernels (ma32::k_cond: csrc/kernels.h at MA_WL = 32, in the three
 capi_<PRIME>_w32 objects): what tests/test_ct_audit.py asserts for the 64-bit k_cond -- no branch on lane data, no exec mask narrowed
 by lane data, nothing unclassified; the only exec-mask / lane-index branches are those of the grid-stride loop (`t < n`)."""
 import os

@@ -1,4 +1,4 @@
-"""The shared inversion of the 32-bit word form on the GPU (csrc/kernels32.h k_inv_simul behind modinv_<P>_w32_batch): the same words
+"""The shared inversion of the 32-bit word form on the GPU (csrc/kernels.h k_inv_simul at MA_WL = 32 behind modinv_<P>_w32_batch): the same words
 as the per-element kernel for every 32-bit limb pattern, no element spoiling another.
 
 A batch of n = 3 * 16384 + 1237 elements of nres(uniform) with every element of tests/w32_inputs.pool(P) -- arbitrary 32-bit words

@@ -1,6 +1,6 @@
 """The shared inversion and the fused chains of the 32-bit word form, CPU side: what fuse.py emits at wl=32, that it cross-compiles
 for gfx950 inside the register file, that the built library holds ma32::k_inv_simul without spills, and that the in-contract predicate
-of the shared inversion (csrc/kernels32.h inv_in_contract, restated in modarith_amd/params.py) admits what the field functions return
+of the shared inversion (csrc/kernels.h inv_in_contract, restated in modarith_amd/params.py) admits what the field functions return
 -- so that the shared path is the path a real batch takes -- and is safe at the edge of what it admits (host build of csrc/field.h)."""
 import os
 import random
