@@ -15,8 +15,9 @@
  *
  * for all 32 functions of field.c (prop flatten modfsb modadd modsub modneg modmli modmul modsqr modcpy modnsqr modpro modinv modqr
  * modsqrt nres redc modis1 modis0 modzer modone modint modcmv modcsw modshl modshr modhaf mod2r modexp modimp modsign modcmp), plus
- * the batched moduniform and modlimbs.  Not offered at this word length: modmuls, the _lazy forms, time_protocol, the ladders and
- * the curve layer (rfc7748_* and ecn_*_get/set speak bytes and do not depend on the word length).
+ * the batched moduniform and modlimbs.  Not offered at this word length: modmuls, the _lazy forms, time_protocol and the ladders
+ * (rfc7748_* speaks bytes and does not depend on the word length).  The curve layer over these fields -- ecn_<c>_w32_* on points of
+ * uint32_t limbs, `curve.py 32` -- is declared in modarith_amd_w32_curve.h.
  *
  * Batched layout: limb-interleaved SoA of uint32_t, FLAT (ld >= n: buf[limb*ld + j]) or TILED (ld < n, a power of two >= 128:
  * buf[((j / ld)*Nlimbs + limb)*ld + (j % ld)]), exactly as in modarith_amd.h with 32-bit words.  An element is 36 bytes (X25519,

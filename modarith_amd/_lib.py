@@ -95,16 +95,21 @@ _SIG_W32 = {fn: args for fn, args in _SIG.items() if fn not in W32_ABSENT}      
 W32_BATCH_FUNCS = tuple(_SIG_W32)
 W32_SCALAR_FUNCS = SCALAR_FUNCS
 W32_UTIL_FUNCS = ("modarith_amd_w32_field_info", "modarith_amd_w32_aos_to_soa", "modarith_amd_w32_soa_to_aos", "modarith_amd_w32_batch_words")
+# ---- the curve layer at word length 32 (include/modarith_amd_w32_curve.h): ecn_<c>_w32_<fn>_batch / ecn_<c>_w32_<fn> over uint32_t points
+W32_CURVES = {"ed25519": (9, 32), "nist256": (9, 32), "ed448": (16, 56)}                   # curve -> (Nlimbs, Nbytes)
+W32_ED_BATCH_FUNCS = tuple(f for f in ED_BATCH_FUNCS if f != "mul2_exact")                 # mul2 IS the reference's walk there
+W32_ED_SCALAR_FUNCS = ED_SCALAR_FUNCS
 
 
-def _declare_curve(lib, C: str) -> None:
+def _declare_curve(lib, C: str, funcs=ED_BATCH_FUNCS) -> None:
     """argtypes / restypes of the batched curve entry points ecn_<C>_*_batch of `lib` (the main library or a curve plug-in)"""
     g = lambda f: getattr(lib, "ecn_%s_%s" % (C, f))
     g("mul_workspace_bytes").argtypes = [c_size_t]
     g("mul_workspace_bytes").restype = c_size_t
     g("mul_batch").argtypes = [_P, _P, c_size_t, c_size_t, _P, c_size_t, _P]
     g("mul2_batch").argtypes = [_P, _P, _P, _P, _P, c_size_t, c_size_t, _P, c_size_t, _P]
-    g("mul2_exact_batch").argtypes = [_P, _P, _P, _P, _P, c_size_t, c_size_t, _P, c_size_t, _P]
+    if "mul2_exact" in funcs:
+        g("mul2_exact_batch").argtypes = [_P, _P, _P, _P, _P, c_size_t, c_size_t, _P, c_size_t, _P]
     g("ran_batch").argtypes = [c_int, _P, c_size_t, c_size_t, _P]
     for f in ("add", "sub", "cpy"):
         g(f + "_batch").argtypes = [_P, _P, c_size_t, c_size_t, _P]
@@ -114,7 +119,7 @@ def _declare_curve(lib, C: str) -> None:
     g("isinf_batch").argtypes = [_P, _P, c_size_t, c_size_t, _P]
     g("set_batch").argtypes = [_P, _P, _P, _P, c_size_t, c_size_t, _P]
     g("get_batch").argtypes = [_P, _P, _P, _P, c_size_t, c_size_t, _P]
-    for f in ED_BATCH_FUNCS:
+    for f in funcs:
         g(f + "_batch").restype = c_int
 
 
@@ -164,6 +169,8 @@ def load() -> ctypes.CDLL:
         h.restype = c_int
     for C in CURVES:
         _declare_curve(lib, C)
+    for C in W32_CURVES:
+        _declare_curve(lib, C + "_w32", W32_ED_BATCH_FUNCS)
     for c in FUSED_CURVES:
         f = getattr(lib, "ecn_%s_mul_get_batch" % c)
         f.argtypes = [_P, _P, _P, _P, _P, c_size_t, c_size_t, _P, c_size_t, _P]

@@ -34,7 +34,12 @@ UNITS = ([(u, u, []) for u in ["capi_common", "capi_ED25519F", "capi_ED25519F2",
          + [(u, "%s_part%d" % (u, part), ["-DMA_CURVE_PART=%d" % part]) for u in _CURVE_UNITS for part in (1, 2, 3)]
          + [("generated/capi_%s" % p, "capi_%s" % p, []) for p in emit.EXTRA_PRIMES]
          # the 32-bit word form (include/modarith_amd_w32.h): one unit per prime over capi_w32.inc, and the entry points of no single prime
-         + [("capi_%s_w32" % p, "capi_%s_w32" % p, []) for p in emit.W32_PRIMES] + [("capi_w32_common", "capi_w32_common", [])])
+         + [("capi_%s_w32" % p, "capi_%s_w32" % p, []) for p in emit.W32_PRIMES] + [("capi_w32_common", "capi_w32_common", [])]
+         # the curve layer at word length 32 (include/modarith_amd_w32_curve.h): capi_curve.inc again, split into the same three parts.  The
+         # objects are named ..._ecn_mul / _mul2 / _rest, not _part<k>: tools/ct_audit.py's sweep of capi_*_part1.o stays the 64-bit one
+         # (tests/test_ct_audit_w32_curve.py audits these)
+         + [("capi_%s_w32_ecn" % c, "capi_%s_w32_ecn_%s" % (c, nm), ["-DMA_CURVE_PART=%d" % part])
+            for c in emit.W32_CURVES for part, nm in ((1, "mul"), (2, "mul2"), (3, "rest"))])
 # longest first, so the pool does not finish on a long tail: measured compile seconds of the slow units (8 jobs on 8 cores; the
 # rest take 10-30 s each)
 _COST = {"capi_SIDH751": 180, "capi_NIST521W_part2": 170, "capi_ED500_part2": 143, "capi_SIDH610": 105, "capi_NIST521W_part1": 91, "capi_CSIDH512": 90,
@@ -49,7 +54,7 @@ def _stamp() -> str:
         for f in sorted(files):
             h.update(f.encode())
             h.update(open(os.path.join(root, f), "rb").read())
-    for header in ("modarith_amd.h", "modarith_amd_w32.h"):
+    for header in ("modarith_amd.h", "modarith_amd_w32.h", "modarith_amd_w32_curve.h"):
         h.update(open(os.path.join(os.path.dirname(HERE), "include", header), "rb").read())
     h.update(" ".join(FLAGS).encode())
     return h.hexdigest()

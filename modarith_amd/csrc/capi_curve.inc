@@ -3,7 +3,20 @@
 // (lower-case token used in the symbol names, as curve.py:344-345 substitutes XXX -> _<curve>_) defined.
 // MA_CURVE_PART splits the unit for the build (the two scalar-multiplication kernels dominate compile time and are
 // compiled in parallel): 1 = only ecn_<c>_mul_batch, 2 = only ecn_<c>_mul2_batch, 3 = everything else; undefined = all.
+//
+// One body for both word lengths (csrc/curve.h): a capi_<CURVE>_w32.hip unit includes generated/w32_curve_<CURVE>.h (MA_WL = 32,
+// classes in ma32) and defines MA_CNAME <c>_w32, which names the entry points of include/modarith_amd_w32_curve.h --
+// ecn_<c>_w32_<fn>[_batch] over uint32_t limbs, ma_point_<c>_w32_t.  There the field is exact for every limb pattern (one launch, no
+// vote), and mul2 IS the reference's own walk: there is no separate mul2_exact.
+#if MA_WL == 32
+#include "../../include/modarith_amd_w32_curve.h"
+typedef ma_spint32 ma_limb;
+#define EB_MUL2_WALK EB(mul2)
+#else
 #include "../../include/modarith_amd.h"
+typedef ma_spint ma_limb;
+#define EB_MUL2_WALK EB(mul2_exact)
+#endif
 #include "capi_common.h"
 #include "edwards.h"
 #include "weierstrass.h"
@@ -23,7 +36,8 @@
 #endif
 
 namespace {
-using namespace ma;
+using namespace MA_NS;
+using namespace ma;             // (the host helpers of capi_common.h)
 using E = MA_CURVE_CLASS;
 using EM = MA_CURVE_MUL_CLASS;
 static_assert(EM::TABLE_WORDS == E::TABLE_WORDS && EM::N == E::N && EM::NB == E::NB, "the multiplication class is the same curve");
@@ -31,6 +45,7 @@ static_assert(EM::TABLE_WORDS == E::TABLE_WORDS && EM::N == E::N && EM::NB == E:
 // EM with the vote at point load, then EX (the same curve on Field<P, false>) for the passes EM left alone
 using EX = typename exact_class<EM>::type;
 constexpr bool GUARDED = !field_is_exact<typename EM::F>::value;
+static_assert(MA_WL == 64 || !GUARDED, "the 32-bit field has one product policy, exact for every limb pattern");
 static_assert(EX::TABLE_WORDS == EM::TABLE_WORDS && EX::SLAB_WORDS == EM::SLAB_WORDS && EX::NDIG == EM::NDIG, "the exact class shares the table geometry");
 constexpr int NL = E::N;
 constexpr int NB = E::NB;
@@ -68,14 +83,14 @@ int launch_op(const spint* Q, spint* P, size_t n, size_t ld, void* st, const cha
 extern "C" {
 
 #if !defined(MA_CURVE_PART) || MA_CURVE_PART == 3
-size_t ES(mul_workspace_bytes)(size_t n) { return mul_lanes(n) * E::TABLE_WORDS * sizeof(spint); }
+size_t ES(mul_workspace_bytes)(size_t n) { return mul_lanes(n) * E::TABLE_BYTES; }
 #endif
 
 #if !defined(MA_CURVE_PART) || MA_CURVE_PART == 1
-int EB(mul)(const char* e, ma_spint* P, size_t n, size_t ld, void* workspace, size_t workspace_bytes, void* st) {
+int EB(mul)(const char* e, ma_limb* P, size_t n, size_t ld, void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
     const size_t lanes = mul_lanes(n);
-    if (workspace == nullptr || workspace_bytes < lanes * E::TABLE_WORDS * sizeof(spint)) {
+    if (workspace == nullptr || workspace_bytes < lanes * E::TABLE_BYTES) {
         set_error("ecn mul: workspace too small (see ecn_<curve>_mul_workspace_bytes)");
         return (int)hipErrorInvalidValue;
     }
@@ -91,12 +106,12 @@ int EB(mul)(const char* e, ma_spint* P, size_t n, size_t ld, void* workspace, si
     return check_launch("ecn mul");
 }
 #endif
-#if !defined(MA_CURVE_PART) || MA_CURVE_PART == 2
-int EB(mul2)(const char* e, const ma_spint* P, const char* f, const ma_spint* Q, ma_spint* R, size_t n, size_t ld,
+#if (!defined(MA_CURVE_PART) || MA_CURVE_PART == 2) && MA_WL == 64
+int EB(mul2)(const char* e, const ma_limb* P, const char* f, const ma_limb* Q, ma_limb* R, size_t n, size_t ld,
              void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
     const size_t lanes = mul_lanes(n);
-    if (workspace == nullptr || workspace_bytes < lanes * E::TABLE_WORDS * sizeof(spint)) {
+    if (workspace == nullptr || workspace_bytes < lanes * E::TABLE_BYTES) {
         set_error("ecn mul2: workspace too small (see ecn_<curve>_mul_workspace_bytes)");
         return (int)hipErrorInvalidValue;
     }
@@ -111,12 +126,14 @@ int EB(mul2)(const char* e, const ma_spint* P, const char* f, const ma_spint* Q,
     }
     return check_launch("ecn mul2");
 }
+#endif
+#if !defined(MA_CURVE_PART) || MA_CURVE_PART == 2
 // the same with the reference's own joint-sparse-form walk (csrc/curve.h mul2_exact): the reference's projective limbs, variable time
-int EB(mul2_exact)(const char* e, const ma_spint* P, const char* f, const ma_spint* Q, ma_spint* R, size_t n, size_t ld,
+int EB_MUL2_WALK(const char* e, const ma_limb* P, const char* f, const ma_limb* Q, ma_limb* R, size_t n, size_t ld,
              void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
     const size_t lanes = mul_lanes(n);
-    if (workspace == nullptr || workspace_bytes < lanes * E::TABLE_WORDS * sizeof(spint)) {
+    if (workspace == nullptr || workspace_bytes < lanes * E::TABLE_BYTES) {
         set_error("ecn mul2_exact: workspace too small (see ecn_<curve>_mul_workspace_bytes)");
         return (int)hipErrorInvalidValue;
     }
@@ -133,32 +150,32 @@ int EB(mul2_exact)(const char* e, const ma_spint* P, const char* f, const ma_spi
 }
 #endif
 #if !defined(MA_CURVE_PART) || MA_CURVE_PART == 3
-int EB(ran)(int r, ma_spint* P, size_t n, size_t ld, void* st) {
+int EB(ran)(int r, ma_limb* P, size_t n, size_t ld, void* st) {
     if (n == 0) return 0;
     k_ed_ran<E><<<grid_for(n), BLOCK, 0, (hipStream_t)st>>>(r, P, n, ld);
     return check_launch("ecn ran");
 }
-int EB(add)(const ma_spint* Q, ma_spint* P, size_t n, size_t ld, void* st) { return launch_op<ED_ADD>(Q, P, n, ld, st, "ecn add"); }
-int EB(sub)(const ma_spint* Q, ma_spint* P, size_t n, size_t ld, void* st) { return launch_op<ED_SUB>(Q, P, n, ld, st, "ecn sub"); }
-int EB(cpy)(const ma_spint* Q, ma_spint* P, size_t n, size_t ld, void* st) { return launch_op<ED_CPY>(Q, P, n, ld, st, "ecn cpy"); }
-int EB(dbl)(ma_spint* P, size_t n, size_t ld, void* st) { return launch_op<ED_DBL>(nullptr, P, n, ld, st, "ecn dbl"); }
-int EB(neg)(ma_spint* P, size_t n, size_t ld, void* st) { return launch_op<ED_NEG>(nullptr, P, n, ld, st, "ecn neg"); }
-int EB(inf)(ma_spint* P, size_t n, size_t ld, void* st) { return launch_op<ED_INF>(nullptr, P, n, ld, st, "ecn inf"); }
-int EB(gen)(ma_spint* P, size_t n, size_t ld, void* st) { return launch_op<ED_GEN>(nullptr, P, n, ld, st, "ecn gen"); }
-int EB(cof)(ma_spint* P, size_t n, size_t ld, void* st) { return launch_op<ED_COF>(nullptr, P, n, ld, st, "ecn cof"); }
-int EB(affine)(ma_spint* P, size_t n, size_t ld, void* st) { return launch_op<ED_AFFINE>(nullptr, P, n, ld, st, "ecn affine"); }
+int EB(add)(const ma_limb* Q, ma_limb* P, size_t n, size_t ld, void* st) { return launch_op<ED_ADD>(Q, P, n, ld, st, "ecn add"); }
+int EB(sub)(const ma_limb* Q, ma_limb* P, size_t n, size_t ld, void* st) { return launch_op<ED_SUB>(Q, P, n, ld, st, "ecn sub"); }
+int EB(cpy)(const ma_limb* Q, ma_limb* P, size_t n, size_t ld, void* st) { return launch_op<ED_CPY>(Q, P, n, ld, st, "ecn cpy"); }
+int EB(dbl)(ma_limb* P, size_t n, size_t ld, void* st) { return launch_op<ED_DBL>(nullptr, P, n, ld, st, "ecn dbl"); }
+int EB(neg)(ma_limb* P, size_t n, size_t ld, void* st) { return launch_op<ED_NEG>(nullptr, P, n, ld, st, "ecn neg"); }
+int EB(inf)(ma_limb* P, size_t n, size_t ld, void* st) { return launch_op<ED_INF>(nullptr, P, n, ld, st, "ecn inf"); }
+int EB(gen)(ma_limb* P, size_t n, size_t ld, void* st) { return launch_op<ED_GEN>(nullptr, P, n, ld, st, "ecn gen"); }
+int EB(cof)(ma_limb* P, size_t n, size_t ld, void* st) { return launch_op<ED_COF>(nullptr, P, n, ld, st, "ecn cof"); }
+int EB(affine)(ma_limb* P, size_t n, size_t ld, void* st) { return launch_op<ED_AFFINE>(nullptr, P, n, ld, st, "ecn affine"); }
 
-int EB(cmp)(const ma_spint* P, const ma_spint* Q, int* out, size_t n, size_t ld, void* st) {
+int EB(cmp)(const ma_limb* P, const ma_limb* Q, int* out, size_t n, size_t ld, void* st) {
     if (n == 0) return 0;
     k_ed_pred<E, true><<<grid_for(n), BLOCK, 0, (hipStream_t)st>>>(P, Q, out, n, ld);
     return check_launch("ecn cmp");
 }
-int EB(isinf)(const ma_spint* P, int* out, size_t n, size_t ld, void* st) {
+int EB(isinf)(const ma_limb* P, int* out, size_t n, size_t ld, void* st) {
     if (n == 0) return 0;
     k_ed_pred<E, false><<<grid_for(n), BLOCK, 0, (hipStream_t)st>>>(P, nullptr, out, n, ld);
     return check_launch("ecn isinf");
 }
-int EB(set)(const int* s, const char* x, const char* y, ma_spint* P, size_t n, size_t ld, void* st) {
+int EB(set)(const int* s, const char* x, const char* y, ma_limb* P, size_t n, size_t ld, void* st) {
     if (n == 0) return 0;
     if (!rec_aligned(x) || !rec_aligned(y)) { set_error("ecn set: records must be 8-byte aligned"); return (int)hipErrorInvalidValue; }
     const unsigned char* xw = reinterpret_cast<const unsigned char*>(x);
@@ -172,7 +189,7 @@ int EB(set)(const int* s, const char* x, const char* y, ma_spint* P, size_t n, s
     } else { set_error("ecn set: x and y are both NULL"); return (int)hipErrorInvalidValue; }
     return check_launch("ecn set");
 }
-int EB(get)(ma_spint* P, char* x, char* y, int* sign, size_t n, size_t ld, void* st) {
+int EB(get)(ma_limb* P, char* x, char* y, int* sign, size_t n, size_t ld, void* st) {
     if (n == 0) return 0;
     if (!rec_aligned(x) || !rec_aligned(y)) { set_error("ecn get: records must be 8-byte aligned"); return (int)hipErrorInvalidValue; }
     k_ed_get<E><<<grid_for(n), BLOCK, 0, (hipStream_t)st>>>(P, reinterpret_cast<unsigned char*>(x), reinterpret_cast<unsigned char*>(y), sign, n, ld);
@@ -251,7 +268,7 @@ void ES(mul2)(const char* e, EPOINT* P, const char* f, EPOINT* Q, EPOINT* R) {
     s.h2d(df, f, NB);
     // one element: no lanes to keep in step, so the scalar entry point -- the reference's own signature -- takes the reference's own
     // walk (mul2_exact) and returns the reference's limbs
-    if (!s.bad) s.check(EB(mul2_exact)(de, dp, df, dq, dr, 1, 1, ws, wsb, nullptr), "ecn mul2");
+    if (!s.bad) s.check(EB_MUL2_WALK(de, dp, df, dq, dr, 1, 1, ws, wsb, nullptr), "ecn mul2");
     s.d2h(R, dr, sizeof(EPOINT));
 }
 void ES(ran)(int r, EPOINT* P) {

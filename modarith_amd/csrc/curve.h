@@ -7,11 +7,21 @@
 // [wave][entry][coord][limb][lane] (coalesced 512-byte rows; sized to the resident grid so it stays in the 256 MiB
 // Infinity Cache) and is scanned in full on every lookup: the table index never forms an address, selection is
 // lane-predicated modcmv.  The recoded scalar digits live in LDS (one byte per window per lane).
+//
+// One text for both word lengths of csrc/field.h (as kernels.h): compiled with MA_WL = 64 (namespace ma, the default: a 64-bit unit sees
+// what it always saw) or MA_WL = 32 (namespace ma32; the reference's `curve.py 32 <CURVE>`, a point = three arrays of uint32_t limbs;
+// capi_curve_w32.inc).  What the word length changes:
+//   * the limbs of a point in HBM and in the window tables are spint: at 32 bits a table row [limb][64 lanes] is 256 bytes, one
+//     global_load_dword per limb (MA_W32_TABLE_PACKED: two limbs per 64-bit word, 512-byte dwordx2 rows as at 64 bits; Table below);
+//   * NOT the scalar records: they travel as 64-bit words at either word length (word_t: NW, shl_words, recode, jsf_digits), and the
+//     LDS digit columns are the same;
+//   * the limb contract folds away: the 32-bit field has ONE product policy, exact for every 32-bit limb pattern (field_is_exact), so
+//     GUARD is 0, there is no vote, no second launch and no resident half-limb form -- a 32-bit limb already is one register.
 #pragma once
 #include "field.h"
 #include "kernels.h"
 
-namespace ma {
+namespace MA_NS {
 
 // scalar(i): i again, pinned into an SGPR.  The window counters of the multiplication loops are wave-uniform, but feed the LDS address of
 // the window's digit, so the compiler may keep them in a VGPR and close the loop with a carry-out vote (v_subrev_co + s_cbranch_vccz):
@@ -46,11 +56,11 @@ struct CurveOps {
     static constexpr int PADB = 8 * NW - NB;         // unused top bytes of the top word (6 for the 66-byte NIST521 records)
     // v <<= S over W words, S a compile-time bit count
     template <int S, int W>
-    static MA_DEV void shl_words(spint* v) {
+    static MA_DEV void shl_words(word_t* v) {
         constexpr int ws = S / 64, bs = S % 64;
         static_for<0, W>([&](auto KK) {
             constexpr int k = W - 1 - KK;
-            spint x = 0;
+            word_t x = 0;
             if constexpr (k - ws >= 0) x = v[k - ws] << bs;
             if constexpr (bs != 0 && k - ws - 1 >= 0) x |= v[k - ws - 1] >> (64 - bs);
             v[k] = x;
@@ -86,11 +96,24 @@ struct CurveOps {
     // [entry][coord][limb][64 lanes]: the slab base is wave-uniform (SGPRs), a lane adds 8 * lane, and entry / coordinate / limb
     // are compile-time or loop-uniform offsets -- the loads of a table scan need no per-lane address arithmetic (one
     // global_load_dwordx2 v, v_lane, s[base] offset:imm per limb), and each is one contiguous 512-byte row.
-    static constexpr size_t ENTRY_WORDS = (size_t)3 * N * 64;            // one table entry of one wave
-    static constexpr size_t TABLE_WORDS = 2 * 9 * 3 * N;                 // per lane: room for the two tables of mul2
+    // A row holds one limb of 64 lanes -- at 32-bit limbs 256 bytes -- or, at word length 32 with MA_W32_TABLE_PACKED defined, two limbs
+    // packed into one 64-bit word (limb 2i low, 2i+1 high; an odd N leaves the last high half zero): 512-byte rows as at 64 bits and half
+    // as many load instructions per scan, for a table of ceil(N/2) * 8 instead of N * 4 bytes per coordinate.  docs/curve_layer.md has
+    // the measurement that chose between the two.
+#if MA_WL == 32 && defined(MA_W32_TABLE_PACKED)
+    static constexpr bool PACKED = true;
+    using row_t = uint64_t;
+#else
+    static constexpr bool PACKED = false;
+    using row_t = spint;
+#endif
+    static constexpr int ROWS = PACKED ? (N + 1) / 2 : N;                // rows of a coordinate
+    static constexpr size_t ENTRY_WORDS = (size_t)3 * ROWS * 64;         // one table entry of one wave (words = row_t)
+    static constexpr size_t TABLE_WORDS = 2 * 9 * 3 * ROWS;              // per lane: room for the two tables of mul2
     static constexpr size_t SLAB_WORDS = 64 * TABLE_WORDS;               // per wave
+    static constexpr size_t TABLE_BYTES = TABLE_WORDS * sizeof(row_t);   // per lane
     struct Table {
-        spint* base;       // slab of this wave (table of mul, or first / second table of mul2): wave-uniform
+        row_t* base;       // slab of this wave (table of mul, or first / second table of mul2): wave-uniform
         unsigned lane;     // 0..63
         // here(): the lane offset as a value born at this access -- otherwise the row addresses (an entry of an 8- or 9-limb curve
         // spans 12-14 KB, beyond one base register's +-4 KB immediate range) are loop-invariant, get hoisted to the top of the
@@ -103,7 +126,20 @@ struct CurveOps {
             return l;
         }
         MA_DEV void put(int k, const Point& w) const {
-            spint* q = base + (size_t)k * ENTRY_WORDS + here();
+            row_t* q = base + (size_t)k * ENTRY_WORDS + here();
+            if constexpr (PACKED) {
+                auto two = [](const limb_t* h, auto I) -> row_t {
+                    row_t v = (row_t)F::pack(h, 2 * I);
+                    if constexpr (2 * I + 1 < N) v |= (row_t)F::pack(h, 2 * I + 1) << 32;
+                    return v;
+                };
+                static_for<0, ROWS>([&](auto I) {
+                    q[(0 * ROWS + I) * 64] = two(w.x, I);
+                    q[(1 * ROWS + I) * 64] = two(w.y, I);
+                    q[(2 * ROWS + I) * 64] = two(w.z, I);
+                });
+                return;
+            }
             static_for<0, N>([&](auto I) {
                 q[(0 * N + I) * 64] = F::pack(w.x, I);
                 q[(1 * N + I) * 64] = F::pack(w.y, I);
@@ -111,7 +147,19 @@ struct CurveOps {
             });
         }
         MA_DEV void get(int k, Point& w) const {
-            const spint* q = base + (size_t)k * ENTRY_WORDS + here();
+            const row_t* q = base + (size_t)k * ENTRY_WORDS + here();
+            if constexpr (PACKED) {
+                auto two = [](row_t v, limb_t* h, auto I) {
+                    F::unpack((spint)v, h, 2 * I);
+                    if constexpr (2 * I + 1 < N) F::unpack((spint)(v >> 32), h, 2 * I + 1);
+                };
+                static_for<0, ROWS>([&](auto I) {
+                    two(q[(0 * ROWS + I) * 64], w.x, I);
+                    two(q[(1 * ROWS + I) * 64], w.y, I);
+                    two(q[(2 * ROWS + I) * 64], w.z, I);
+                });
+                return;
+            }
             static_for<0, N>([&](auto I) {
                 F::unpack(q[(0 * N + I) * 64], w.x, I);
                 F::unpack(q[(1 * N + I) * 64], w.y, I);
@@ -167,11 +215,11 @@ struct CurveOps {
     // ds_read_i8 -- no scalar words or carry masks stay in registers during the multiplication.  Each lane reads only what it wrote
     // itself (the kernels run one wave per workgroup), so no barrier is involved.
     static constexpr int NDIG = 2 * NB + 1;
-    static MA_DEV void recode(const spint* ew, signed char* dg) {
+    static MA_DEV void recode(const word_t* ew, signed char* dg) {
         unsigned c = 0;
         static_for<0, NW>([&](auto K) {
             constexpr int cnt = (2 * NB - 16 * K) < 16 ? (2 * NB - 16 * K) : 16;
-            spint word = ew[K];
+            word_t word = ew[K];
             signed char* d = dg + (size_t)(16 * K) * 64;
 #pragma unroll 1
             for (int j = 0; j < cnt; j++) {
@@ -237,20 +285,20 @@ struct CurveOps {
     // VGPRs for the 521-bit field) are dead by the time the walk starts.
     static constexpr int JSF_TOP = 8 * NB + 7;                    // index of the highest digit (edwards.c:497)
     static constexpr int JSF_BYTES = (JSF_TOP + 1) / 2;
-    static MA_DEV void jsf_digits(const spint* ew, const spint* fw, unsigned char* dj) {
+    static MA_DEV void jsf_digits(const word_t* ew, const word_t* fw, unsigned char* dj) {
         constexpr int NX = NW + 1;                        // 3e needs two more bits than e
-        spint a[NX], a3[NX], b[NX], b3[NX];
+        word_t a[NX], a3[NX], b[NX], b3[NX];
         static_for<0, NX>([&](auto K) { a[K] = K < NW ? ew[K < NW ? K : 0] : 0; b[K] = K < NW ? fw[K < NW ? K : 0] : 0; });
         {   // 3x = x + 2x over NX words
-            spint ca = 0, cb = 0;
+            word_t ca = 0, cb = 0;
             static_for<0, NX>([&](auto K) {
-                const spint ta = (a[K] << 1) | (K > 0 ? a[K > 0 ? K - 1 : 0] >> 63 : 0);
-                const spint tb = (b[K] << 1) | (K > 0 ? b[K > 0 ? K - 1 : 0] >> 63 : 0);
-                const spint sa = a[K] + ta, sa2 = sa + ca;
-                ca = (spint)(sa < ta) | (spint)(sa2 < sa);
+                const word_t ta = (a[K] << 1) | (K > 0 ? a[K > 0 ? K - 1 : 0] >> 63 : 0);
+                const word_t tb = (b[K] << 1) | (K > 0 ? b[K > 0 ? K - 1 : 0] >> 63 : 0);
+                const word_t sa = a[K] + ta, sa2 = sa + ca;
+                ca = (word_t)(sa < ta) | (word_t)(sa2 < sa);
                 a3[K] = sa2;
-                const spint sb = b[K] + tb, sb2 = sb + cb;
-                cb = (spint)(sb < tb) | (spint)(sb2 < sb);
+                const word_t sb = b[K] + tb, sb2 = sb + cb;
+                cb = (word_t)(sb < tb) | (word_t)(sb2 < sb);
                 b3[K] = sb2;
             });
         }
@@ -360,7 +408,7 @@ __global__ __launch_bounds__(64, (GUARD < 0 ? 2 : MA_MUL_WPS)) void k_ed_mul(con
     // double multiplications too (two / JSF arrays per workgroup): ADVICE of round 4
     static_assert((size_t)4 * MA_MUL_WPS * 2 * E::NDIG * 64 <= (size_t)160 * 1024, "LDS budget of the resident scalar-multiplication grid");
     __shared__ signed char digs[E::NDIG * 64];
-    const typename E::Table W{ws + (size_t)blockIdx.x * E::SLAB_WORDS, threadIdx.x};
+    const typename E::Table W{reinterpret_cast<typename E::row_t*>(ws) + (size_t)blockIdx.x * E::SLAB_WORDS, threadIdx.x};
     signed char* dg = digs + threadIdx.x;
     // base: the wave's first element of this pass, wave-uniform (SGPRs); a lane's element index base + lane is formed where it is used
     // (W.here(): the lane number as a fresh value), so no 64-bit index or address stays in VGPRs across the multiplication
@@ -370,7 +418,7 @@ __global__ __launch_bounds__(64, (GUARD < 0 ? 2 : MA_MUL_WPS)) void k_ed_mul(con
             if ((MA_WAVE_ALL(E::limbs_ok(Pb, ld, base + W.here())) != 0) != (GUARD > 0)) continue;
         }
         {
-            spint ew[E::NW];
+            word_t ew[E::NW];
             load_be_record<typename E::P>(e, base + W.here(), ew);         // big-endian byte record -> little-endian words
             E::recode(ew, dg);
         }
@@ -386,7 +434,7 @@ __global__ __launch_bounds__(64, (GUARD < 0 ? 2 : MA_MUL_WPS)) void k_ed_mul2(co
                                                 size_t n, size_t ld, spint* ws) {
     using E = Crv;
     __shared__ signed char digs[2 * E::NDIG * 64];
-    const typename E::Table W{ws + (size_t)blockIdx.x * E::SLAB_WORDS, threadIdx.x};
+    const typename E::Table W{reinterpret_cast<typename E::row_t*>(ws) + (size_t)blockIdx.x * E::SLAB_WORDS, threadIdx.x};
     signed char* de = digs + threadIdx.x;
     signed char* df = de + E::NDIG * 64;
     for (size_t base = (size_t)blockIdx.x * 64; base < n; base += (size_t)gridDim.x * 64) {
@@ -396,7 +444,7 @@ __global__ __launch_bounds__(64, (GUARD < 0 ? 2 : MA_MUL_WPS)) void k_ed_mul2(co
             if ((MA_WAVE_ALL(ok) != 0) != (GUARD > 0)) continue;
         }
         {
-            spint ew[E::NW];
+            word_t ew[E::NW];
             load_be_record<typename E::P>(e, base + W.here(), ew);
             E::recode(ew, de);
             load_be_record<typename E::P>(f, base + W.here(), ew);
@@ -419,7 +467,7 @@ __global__ __launch_bounds__(64, (GUARD < 0 ? 2 : MA_MUL_WPS)) void k_ed_mul2x(c
                                                  size_t n, size_t ld, spint* ws) {
     using E = Crv;
     __shared__ unsigned char digs[E::JSF_BYTES * 64];
-    const typename E::Table W{ws + (size_t)blockIdx.x * E::SLAB_WORDS, threadIdx.x};
+    const typename E::Table W{reinterpret_cast<typename E::row_t*>(ws) + (size_t)blockIdx.x * E::SLAB_WORDS, threadIdx.x};
     unsigned char* dj = digs + threadIdx.x;
     for (size_t base = (size_t)blockIdx.x * 64; base < n; base += (size_t)gridDim.x * 64) {
         if (base + W.here() >= n) continue;
@@ -428,7 +476,7 @@ __global__ __launch_bounds__(64, (GUARD < 0 ? 2 : MA_MUL_WPS)) void k_ed_mul2x(c
             if ((MA_WAVE_ALL(ok) != 0) != (GUARD > 0)) continue;
         }
         {
-            spint ew[E::NW], fw[E::NW];
+            word_t ew[E::NW], fw[E::NW];
             load_be_record<typename E::P>(e, base + W.here(), ew);
             load_be_record<typename E::P>(f, base + W.here(), fw);
             E::jsf_digits(ew, fw, dj);
@@ -454,8 +502,17 @@ __global__ __launch_bounds__(BLOCK) void k_ed_ran(int r, spint* Pb, size_t n, si
 }
 
 enum { ED_ADD = 0, ED_SUB, ED_DBL, ED_NEG, ED_INF, ED_GEN, ED_COF, ED_AFFINE, ED_CPY };
+// At 32-bit limbs two points and the temporaries of a formula are 100-250 registers before any product: with nothing but the workgroup
+// size to bound it the allocator spreads add / sub / dbl over 268-294 registers, accumulation registers included (one wave per SIMD).
+// Two waves per SIMD cap the kernel at 256 architectural registers -- except add / sub of the 16-limb field, which would then spill
+// 16-18 registers; those two stay unbounded (tools/spill_allowlist.json).  The 64-bit kernels keep the bound they always had.
+#if MA_WL == 32
+#define MA_ED_OP_BOUNDS __launch_bounds__(BLOCK, ((Crv::N > 9 && (OP == ED_ADD || OP == ED_SUB)) ? 1 : 2))
+#else
+#define MA_ED_OP_BOUNDS __launch_bounds__(BLOCK)
+#endif
 template <class Crv, int OP>
-__global__ __launch_bounds__(BLOCK) void k_ed_op(const spint* Qb, spint* Pb, size_t n, size_t ld) {
+__global__ MA_ED_OP_BOUNDS void k_ed_op(const spint* Qb, spint* Pb, size_t n, size_t ld) {
     using E = Crv;
     for (size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x; t < n; t += (size_t)gridDim.x * BLOCK) {
         typename E::Point p, q;
@@ -496,7 +553,8 @@ __global__ __launch_bounds__(BLOCK) void k_ed_set(const int* s, const unsigned c
     using F = typename E::F;
     constexpr int NW = E::NW;
     for (size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x; t < n; t += (size_t)gridDim.x * BLOCK) {
-        spint X[E::N], Y[E::N], w[NW];
+        spint X[E::N], Y[E::N];
+        word_t w[NW];
         if constexpr (MODE != 2) {
             load_be_record<typename E::P>(xb, t, w);
             (void)F::modimp_words(w, X);
@@ -522,7 +580,7 @@ __global__ __launch_bounds__(BLOCK) void k_ed_get(spint* Pb, unsigned char* xb, 
         E::load(Pb, ld, t, p);
         E::affine(p);
         E::store(Pb, ld, t, p);
-        spint w[NW];
+        word_t w[NW];
         if (xb) {
             F::modexp_words(p.x, w);
             store_be_record<typename E::P>(xb, t, w);
@@ -540,4 +598,4 @@ __global__ __launch_bounds__(BLOCK) void k_ed_get(spint* Pb, unsigned char* xb, 
     }
 }
 
-}  // namespace ma
+}  // namespace MA_NS

@@ -7,7 +7,7 @@
 #pragma once
 #include "curve.h"
 
-namespace ma {
+namespace MA_NS {
 
 template <class C, class F_ = Field<typename C::FieldParams, true>>
 struct Edwards : CurveOps<Edwards<C, F_>, typename C::FieldParams, F_> {
@@ -172,4 +172,4 @@ struct Edwards : CurveOps<Edwards<C, F_>, typename C::FieldParams, F_> {
 };
 template <class C, class F_> struct exact_class<Edwards<C, F_>> { using type = Edwards<C, Field<typename C::FieldParams, false>>; };   // curve.h "the limb contract"
 
-}  // namespace ma
+}  // namespace MA_NS

@@ -8,7 +8,7 @@
 #pragma once
 #include "curve.h"
 
-namespace ma {
+namespace MA_NS {
 
 template <class C, class F_ = Field<typename C::FieldParams, true>>     // F_: the limb form, or a resident half-limb form for the scalar multiplications (tried for P-256 in round 4 and dropped: docs/curve_layer.md)
 struct Weierstrass : CurveOps<Weierstrass<C, F_>, typename C::FieldParams, F_> {
@@ -269,4 +269,4 @@ struct Weierstrass : CurveOps<Weierstrass<C, F_>, typename C::FieldParams, F_> {
 };
 template <class C, class F_> struct exact_class<Weierstrass<C, F_>> { using type = Weierstrass<C, Field<typename C::FieldParams, false>>; };   // curve.h "the limb contract"
 
-}  // namespace ma
+}  // namespace MA_NS

@@ -24,11 +24,28 @@ class Edwards:
     """Batched curve API (one object per stream: the window-table workspaces it allocates for `mul`, `mul_get`, ... are reused by the
     next call, so two host threads / streams driving the SAME object concurrently would share them; the C-ABI takes the workspace
     explicitly).  Despite the name it serves every built curve of the reference's curve layer:
-    Edwards ("ED25519", "ED448", "NUMS256E", "ED248", "ED376", "ED500") and short Weierstrass ("NIST256", "NIST384", "NIST521", "SECP256K1", "NUMS256W").  `Curve` is an alias."""
+    Edwards ("ED25519", "ED448", "NUMS256E", "ED248", "ED376", "ED500") and short Weierstrass ("NIST256", "NIST384", "NIST521", "SECP256K1", "NUMS256W").  `Curve` is an alias.
 
-    def __init__(self, curve: str, device: Optional[torch.device] = None):
+    wl=32: the same API on the points of `curve.py 32 <CURVE>` -- torch.int32 tensors [3, Nlimbs, n] of 29- / 28-bit limbs (ED25519 and
+    NIST256: 9 limbs, ED448: 16; include/modarith_amd_w32_curve.h), the reference's limbs for every 32-bit limb pattern.  mul2 is the
+    reference's own walk there (`exact` changes nothing); the fused byte-output forms are offered at word length 64 only."""
+
+    W32 = ("ED25519", "NIST256", "ED448")       # curves built at word length 32
+
+    def __init__(self, curve: str, device: Optional[torch.device] = None, wl: int = 64):
         self.name = curve.lower()
-        if self.name in _lib.CURVES:
+        if wl not in (64, 32):
+            raise ValueError("wl must be 64 or 32")
+        self.wl = wl
+        self.dtype = torch.int64 if wl == 64 else torch.int32
+        self._sym = self.name if wl == 64 else self.name + "_w32"      # ecn_<sym>_<fn>_batch
+        if wl == 32:
+            if curve.upper() not in self.W32:
+                raise ValueError("curve %r is not built at word length 32 (built there: %s)" % (curve, ", ".join(self.W32)))
+            self.lib = _lib.load()
+            self.N, self.nbytes = _lib.W32_CURVES[self.name]
+            self._field = None
+        elif self.name in _lib.CURVES:
             self.lib = _lib.load()
             self.N, self.nbytes = _lib.CURVES[self.name]
             self._field = None
@@ -47,14 +64,14 @@ class Edwards:
 
     # ------------------------------------------------------------------ plumbing
     def empty(self, n: int) -> torch.Tensor:
-        return torch.empty((3, self.N, n), dtype=torch.int64, device=self.device)
+        return torch.empty((3, self.N, n), dtype=self.dtype, device=self.device)
 
     def _chk(self, *ps: torch.Tensor) -> int:
         n = ps[0].shape[2]
         for p in ps:
-            if p.dtype != torch.int64 or p.dim() != 3 or p.shape[0] != 3 or p.shape[1] != self.N or p.shape[2] != n \
+            if p.dtype != self.dtype or p.dim() != 3 or p.shape[0] != 3 or p.shape[1] != self.N or p.shape[2] != n \
                     or not p.is_cuda or not p.is_contiguous():
-                raise ValueError("expected contiguous int64 device tensors of shape [3, %d, n]" % self.N)
+                raise ValueError("expected contiguous %s device tensors of shape [3, %d, n]" % (str(self.dtype).replace("torch.", ""), self.N))
             if p.device != self.device:
                 raise ValueError("batch on %s, curve bound to %s" % (p.device, self.device))
         return n
@@ -67,9 +84,9 @@ class Edwards:
         return b.data_ptr()
 
     def _call(self, fn: str, *args):
-        f = getattr(self.lib, "ecn_%s_%s_batch" % (self.name, fn))
+        f = getattr(self.lib, "ecn_%s_%s_batch" % (self._sym, fn))
         with torch.cuda.device(self.device):          # the C-ABI launches on the calling thread's current device
-            _lib.check(f(*args), "ecn_%s_%s_batch" % (self.name, fn))
+            _lib.check(f(*args), "ecn_%s_%s_batch" % (self._sym, fn))
 
     def _scalars(self, e: Optional[torch.Tensor], n: int):
         if e is None:
@@ -120,7 +137,7 @@ class Edwards:
         self._chk(P)
         up = self.name.upper()
         fname = self._field or (curves.CURVES[up] if up in curves.CURVES else curves.W_CURVES[up]).field
-        F = Field(fname, device=self.device)
+        F = Field(fname, device=self.device) if self.wl == 64 else Field(fname, device=self.device, wl=32)
         return F.modlimbs(P[0]) & F.modlimbs(P[1]) & F.modlimbs(P[2])
 
     def dbl(self, P): return self._un("dbl", P)
@@ -131,7 +148,7 @@ class Edwards:
     def mul(self, e: torch.Tensor, P: torch.Tensor):
         """P = e*P for big-endian scalar records e (constant-time fixed window, edwards.c:435-482)"""
         n = self._chk(P)
-        need = int(getattr(self.lib, "ecn_%s_mul_workspace_bytes" % self.name)(n))
+        need = int(getattr(self.lib, "ecn_%s_mul_workspace_bytes" % self._sym)(n))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         self._call("mul", self._scalars(e, n), P.data_ptr(), n, n, self._ws.data_ptr(), self._ws.numel(), _stream(self.device))
@@ -146,7 +163,7 @@ class Edwards:
         *_get methods): the coordinate limbs of P keep the limb budget (every limb < 2^(Radix+2): `limbs_ok(P)`), as every
         point produced by this library does; limbs fabricated above it are truncated by the 32-bit re-packing, whereas
         mul() reproduces the reference's 64-bit behaviour for them."""
-        if self.name.upper() not in self.FUSED:
+        if self.wl != 64 or self.name.upper() not in self.FUSED:
             raise ValueError("no fused mul_get kernel for %s (available: %s)" % (self.name, ", ".join(self.FUSED)))
         n = self._chk(P)
         x = torch.empty((n, self.nbytes), dtype=torch.uint8, device=self.device) if want_x else None
@@ -165,7 +182,7 @@ class Edwards:
         """ecnXXXgen, ecnXXXmul, ecnXXXget (the opening of key generation and signing, nist256.c:150-161, 214-222, ed448.c:167-184, 196-199) in ONE
         kernel: the affine coordinates of e*G as canonical big-endian byte records and the sign of the omitted coordinate.
         Same bytes as get(mul(e, gen(n))); no doublings (precomputed multiples of G), about four times the rate of mul_get."""
-        if self.name.upper() not in self.FUSEDG:
+        if self.wl != 64 or self.name.upper() not in self.FUSEDG:
             raise ValueError("no fused mulgen_get kernel for %s (available: %s)" % (self.name, ", ".join(self.FUSEDG)))
         if e is None or e.dim() != 2:
             raise ValueError("scalar records are required (uint8 [n, %d], big-endian)" % self.nbytes)
@@ -183,7 +200,7 @@ class Edwards:
         """ecnXXXgen, ecnXXXmul2(e, G, f, Q, R), ecnXXXget (signature verification, nist256.c:251-256, ed448.c:305) in ONE kernel:
         the affine coordinates of e*G + f*Q as canonical big-endian byte records.  Q is not modified.  Same bytes as
         mul2_get(e, gen(n), f, Q); the generator part runs on the fixed-base table."""
-        if self.name.upper() not in self.FUSEDG2:
+        if self.wl != 64 or self.name.upper() not in self.FUSEDG2:
             raise ValueError("no fused mulgen2_get kernel for %s (available: %s)" % (self.name, ", ".join(self.FUSEDG2)))
         n = self._chk(Q)
         x = torch.empty((n, self.nbytes), dtype=torch.uint8, device=self.device) if want_x else None
@@ -202,7 +219,7 @@ class Edwards:
     def mul2_get(self, e, P, f, Q, want_x: bool = True, want_y: bool = True):
         """ecnXXXmul2 followed by ecnXXXget (the verification pattern, ed448.c:305) in ONE kernel: the affine coordinates of
         e*P + f*Q as canonical big-endian byte records and the sign of the omitted coordinate.  P, Q are not modified."""
-        if self.name.upper() not in self.FUSED2:
+        if self.wl != 64 or self.name.upper() not in self.FUSED2:
             raise ValueError("no fused mul2_get kernel for %s (available: %s)" % (self.name, ", ".join(self.FUSED2)))
         n = self._chk(P, Q)
         x = torch.empty((n, self.nbytes), dtype=torch.uint8, device=self.device) if want_x else None
@@ -217,7 +234,7 @@ class Edwards:
         return x, y, sign
 
     def _workspace(self, n: int):
-        need = int(getattr(self.lib, "ecn_%s_mul_workspace_bytes" % self.name)(n))
+        need = int(getattr(self.lib, "ecn_%s_mul_workspace_bytes" % self._sym)(n))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
@@ -229,7 +246,7 @@ class Edwards:
         n = self._chk(P, Q)
         R = torch.empty_like(P)
         ws = self._workspace(n)
-        self._call("mul2_exact" if exact else "mul2", self._scalars(e, n), P.data_ptr(), self._scalars(f, n), Q.data_ptr(), R.data_ptr(), n, n,
+        self._call("mul2_exact" if exact and self.wl == 64 else "mul2", self._scalars(e, n), P.data_ptr(), self._scalars(f, n), Q.data_ptr(), R.data_ptr(), n, n,
                    ws.data_ptr(), ws.numel(), _stream(self.device))
         return R
 

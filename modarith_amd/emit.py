@@ -516,6 +516,46 @@ def wcurve_header_text_of(c) -> str:
     return "\n".join(L) + "\n"
 
 
+# the curve layer at word length 32 (include/modarith_amd_w32_curve.h): curve.py's three curves whose fields are built at that word length
+W32_CURVES = ("ED25519", "NIST256", "ED448")
+
+
+def w32_curve_header_text(name: str) -> str:
+    """csrc/generated/w32_curve_<CURVE>.h: `struct C_<CURVE>_W32` in namespace ma32 -- the constants of curve_<CURVE>.h as limbs of the
+    32-bit field (params.derive(field, wl=32); Montgomery form where that field has one: NIST256 and X448 at this word length),
+    derived from curves.py like the 64-bit ones."""
+    import dataclasses
+    from . import curves
+    edw = name in curves.CURVES
+    c0 = curves.CURVES[name] if edw else curves.W_CURVES[name]
+    c = dataclasses.replace(c0, fp=derive(c0.field, wl=32))
+    assert not c.small_x, "a generator given by a small x needs the field's square root at gen()"
+    L = ["// GENERATED by modarith_amd/emit.py from modarith_amd/curves.py -- do not edit.",
+         ("// Edwards curve %s: %d*x^2 + y^2 = 1 + d*x^2*y^2" % (c.name, c.a) if edw else "// Weierstrass curve %s: y^2 = x^3 %+d*x + b" % (c.name, c.a))
+         + " over the %s field at word length 32 (%d x %d-bit limbs%s)" % (c.field, c.fp.nlimbs, c.fp.radix, ", Montgomery form" if c.fp.montgomery else ""),
+         "#pragma once",
+         '#include "w32_%s.h"' % c.field,
+         "namespace ma32 {",
+         "struct C_%s_W32 {" % c.name,
+         "    using FieldParams = P_%s_W32;" % c.field]
+    if edw:
+        L += ["    static constexpr int A = %d, COF = %d;" % (c.a, c.cof),
+              "    static constexpr bool B_SMALL = %s;" % ("true" if c.small_b else "false"),
+              "    static constexpr int B_INT = %d;       // CONSTANT_B when small (curve.py:256-257)" % (c.d if c.small_b else 0),
+              "    static constexpr int SMALL_X = 0;     // CONSTANT_X when the generator is given by a small x (curve.py:239-240), else 0",
+              _switch("b", "unsigned long long", c.internal(c.d) if not c.small_b else [0] * c.fp.nlimbs, _hexu)]
+    else:
+        L += ["    static constexpr int A = %d, COF = 0;" % c.a,
+              "    static constexpr int SMALL_B = %d;   // curve.py's CONSTANT_B when |b| < 2^28, else 0 (b, b3 below are used)" % (c.b if c.small_b else 0),
+              "    static constexpr int SMALL_X = 0;   // curve.py's CONSTANT_X when the generator is given by a small x, else 0",
+              _switch("b", "unsigned long long", c.internal(c.b), _hexu),
+              _switch("b3", "unsigned long long", c.internal(3 * c.b), _hexu)]
+    L += [_switch("gx", "unsigned long long", c.internal(c.gx), _hexu),
+          _switch("gy", "unsigned long long", c.internal(c.gy), _hexu),
+          "};", "}  // namespace ma32"]
+    return "\n".join(L) + "\n"
+
+
 COMB_CURVES = {"NIST256": (286, 5), "SECP256K1": (0, 5)}      # curve -> (log2 of the Montgomery factor of the fused kernels' field form, window width)
 
 
@@ -723,6 +763,8 @@ def emit_w32(out_dir: str = GEN_DIR, include_dir: str = INCLUDE_DIR) -> List[str
         paths.append(_write(os.path.join(out_dir, "w32_%s.h" % name), header_text(fp)))
         if include_dir:
             paths.append(_write(os.path.join(include_dir, "field_%s_w32.h" % name), field_shim_text(fp)))
+    for name in W32_CURVES:
+        paths.append(_write(os.path.join(out_dir, "w32_curve_%s.h" % name), w32_curve_header_text(name)))
     return paths
 
 
