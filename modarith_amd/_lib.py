@@ -237,24 +237,27 @@ def load() -> ctypes.CDLL:
 _plugins = {}
 
 
-def load_plugin(tag: str, path: str = None) -> ctypes.CDLL:
+def load_plugin(tag: str, path: str = None, wl: int = 64) -> ctypes.CDLL:
     """Load the plug-in of a generated field (modarith_amd.generate): same entry points as a built-in prime, under
-    <fn>_<tag>_batch / <fn>_<tag>_ct.  The main library is loaded first; the plug-in's DT_NEEDED entry resolves to it."""
-    if tag in _plugins:
-        return _plugins[tag]
+    <fn>_<tag>_batch / <fn>_<tag>_ct -- or, wl=32 (generate_w32), <fn>_<tag>_w32_batch / <fn>_<tag>_w32_ct with the tables of the 32-bit
+    word form.  The main library is loaded first; the plug-in's DT_NEEDED entry resolves to it."""
+    if (tag, wl) in _plugins:
+        return _plugins[tag, wl]
+    if wl not in (64, 32):
+        raise ValueError("word length must be 64 or 32")
     load()
     if path is None:
         from .generate import plugin_path
-        path = plugin_path(tag)
+        path = plugin_path(tag, wl=wl)
     if not os.path.exists(path):
-        raise RuntimeError("modarith_amd: no plug-in for %r (%s) -- generate it with `python -m modarith_amd.generate 64 <prime>`. "
-                           "There is no CPU fallback." % (tag, path))
+        raise RuntimeError("modarith_amd: no plug-in for %r (%s) -- generate it with `python -m modarith_amd.generate %s <prime>`. "
+                           "There is no CPU fallback." % (tag, path, "64" if wl == 64 else "w32"))
     lib = ctypes.CDLL(path)
-    for fn, args in _SIG.items():
-        f = getattr(lib, "%s_%s_batch" % (fn, tag))
+    for fn, args in (_SIG if wl == 64 else _SIG_W32).items():
+        f = getattr(lib, "%s_%s%s_batch" % (fn, tag, "" if wl == 64 else "_w32"))
         f.argtypes = args
         f.restype = c_int
-    _plugins[tag] = lib
+    _plugins[tag, wl] = lib
     return lib
 
 

@@ -41,6 +41,14 @@ int pick_ept(size_t n, size_t ld, uintptr_t addr) {
     return 1;
 }
 template <int E> using Width = std::integral_constant<int, E>;
+// widest streaming kernel this unit COMPILES: a generated 32-bit unit names it (MA_W32_EPT_MAX = 1 | 2 | 4, chosen by the driver from
+// the limb count so that no width it builds leaves the register budget: modarith_amd/emit.py w32_ept_max); its ept_cap() clamps to
+// the same figure, so a width that is not compiled is never picked.  Undefined: every width of the word length, as before.
+#ifdef MA_W32_EPT_MAX
+constexpr int EPT_COMPILED = MA_W32_EPT_MAX;
+#else
+constexpr int EPT_COMPILED = 4;
+#endif
 template <class Go>
 int launch_stream(size_t n, size_t ld, uintptr_t addr, const char* what, Go go) {
     if (n == 0) return 0;
@@ -48,8 +56,8 @@ int launch_stream(size_t n, size_t ld, uintptr_t addr, const char* what, Go go) 
     const int ept = pick_ept(n, ld, addr), sb = std::min(stream_block(), stream_block_max(ept));
     const size_t nt = n / ept, done = nt * ept;
     const unsigned grid = grid_for(nt, sb, L.s != 63);
-    if (ept == 4) { if constexpr (MA_WL == 32) go(Width<4>{}, grid, sb, 0, nt, L); }
-    else if (ept == 2) go(Width<2>{}, grid, sb, 0, nt, L);
+    if (ept == 4) { if constexpr (MA_WL == 32 && EPT_COMPILED >= 4) go(Width<4>{}, grid, sb, 0, nt, L); }
+    else if (ept == 2) { if constexpr (EPT_COMPILED >= 2) go(Width<2>{}, grid, sb, 0, nt, L); }
     else go(Width<1>{}, grid, sb, 0, nt, L);
     if (done < n) go(Width<1>{}, 1u, BLOCK, L.off<NL>(done), n - done, Ld(L.ld));
     return check_launch(what);

@@ -32,11 +32,20 @@ constexpr int NB = P::NBYTES;
 // 0.77-0.80 at two and 0.75-0.79 at four elements per lane -- so the wider accesses are kept as alternatives, not used by default.
 // MA_W32_EPT=1|2|4 raises the widest access the library may take and MA_W32_BLOCK=64|128|256|512 sets the workgroup size, for the
 // calls that follow (read at every call): testing and measuring knobs, like MA_FORCE_EXACT of the 64-bit form.  Same words on every path.
+// A generated unit (modarith_amd/generate.py generate_w32) defines MA_W32_EPT_MAX, the widest width its limb count leaves without
+// scratch or accumulation registers (four up to 16 limbs, two for 17 and 18: docs/kernels_field.md 4.5); wider requests are clamped
+// to it and the wider kernels are not compiled (capi_field.inc EPT_COMPILED).
 constexpr int EPT_DEFAULT = 1;
 int ept_cap() {                  // (read at every call: tools/w32_rate.py measures the widths side by side in one process)
     const char* e = getenv("MA_W32_EPT");
     const int x = e ? atoi(e) : 0;
-    return (x == 1 || x == 2 || x == 4) ? x : EPT_DEFAULT;
+    const int cap = (x == 1 || x == 2 || x == 4) ? x : EPT_DEFAULT;
+#ifdef MA_W32_EPT_MAX
+    static_assert(MA_W32_EPT_MAX == 1 || MA_W32_EPT_MAX == 2 || MA_W32_EPT_MAX == 4, "MA_W32_EPT_MAX is 1, 2 or 4");
+    return cap < MA_W32_EPT_MAX ? cap : MA_W32_EPT_MAX;
+#else
+    return cap;
+#endif
 }
 
 // workgroup size of the streaming kernels (MA_W32_BLOCK=64|128|256 overrides it for a process, like MA_W32_EPT)
@@ -47,13 +56,20 @@ int stream_block() {
     return (x == 64 || x == 128 || x == 256 || x == 512) ? x : STREAM_BLOCK_DEFAULT;
 }
 
-constexpr bool INV_SIMUL = true;                // (thresholds and dispatch of the 64-bit form: capi_field.inc)
+// Whether elements of a large batch may share an inversion (kernels.h k_inv_simul).  The admission predicate inv_in_contract is
+// justified prime by prime: by hand for the three built-in primes (the comment above it), by the driver for a generated one
+// (modarith_amd/params.py w32_inv_closure, which writes its verdict into the parameter struct as INV_CLOSED).  A struct without the
+// member is a built-in one; a generated prime whose closure the driver could not show keeps one inversion per element at every
+// batch size -- the same words, under the launch name "modinv(w32)" -- and does not compile the shared kernel at all.
+template <class Q, class = void> struct inv_closed_of : std::true_type {};
+template <class Q> struct inv_closed_of<Q, std::void_t<decltype(Q::INV_CLOSED)>> : std::bool_constant<Q::INV_CLOSED> {};
+constexpr bool INV_SIMUL = inv_closed_of<P>::value;   // (thresholds and dispatch of the 64-bit form: capi_field.inc)
 }  // namespace
 #include "capi_field.inc"
 
 namespace {
 int modinv_each(const spint* x, spint* z, size_t n, size_t ld, void* st) { return launch_unary_heavy<OpInv<P>>(x, z, n, ld, st, "modinv(w32)"); }
-bool inv_may_share() { return true; }
+bool inv_may_share() { return INV_SIMUL; }
 }  // namespace
 
 extern "C" {

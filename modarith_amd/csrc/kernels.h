@@ -596,7 +596,27 @@ __device__ __forceinline__ void load_be_record(const unsigned char* bytes, size_
     if constexpr (NB % 8 == 0) {
         const word_t* src = reinterpret_cast<const word_t*>(bytes) + t * NW;
         static_for<0, NW>([&](auto K) { w[K] = __builtin_bswap64(src[NW - 1 - K]); });
+    } else if constexpr (MA_WL == 32) {
+        // The same, with every byte taken through a register the compiler knows nothing about.  For 30-byte records and 29-bit limbs
+        // (GM240 at word length 32) hipcc folds the OR of the byte loads of limb 0 into one v_perm_b32 whose selector puts byte 28
+        // into bits 24..31 as a filler, ORs byte 26 on top and masks with 2^29 - 1 only: bits 24..28 of the limb then hold
+        // (byte 28 | byte 26) & 0x1f.  Seen in the disassembly and on the device (limb 0 off by 2^28 for one record in two); the
+        // host build of the same text is right.  Opaque bytes keep the fold from forming; the built-in primes of this word length
+        // have records of 32 and 56 bytes and never come here.
+        const unsigned char* src = bytes + t * NB;
+        static_for<0, NW>([&](auto K) { w[K] = 0; });
+        static_for<0, NB>([&](auto B) {
+            constexpr int pos = NB - 1 - B;                 // byte significance (0 = least)
+            uint32_t by = src[B];
+            asm volatile("" : "+v"(by));
+            w[pos / 8] |= (word_t)by << (8 * (pos % 8));
+        });
     } else {
+        // (64-bit words keep the plain form, whose code the change above must not touch.  The same source pattern could fold the same
+        // way: the 30-byte GM240 unit has no v_perm_b32 in k_imp at all, the 66-byte NIST521 unit has seven that nobody has traced
+        // byte by byte.  What guards them is tests/test_gpu_parity.py test_golden_bytes -- the reference's modimp on fixed and random
+        // records for every prime, on the device -- so a compiler that folds them wrongly fails that test; re-inspect the
+        // disassembly of k_imp for the primes whose NBYTES is no multiple of 8 when the compiler changes.)
         const unsigned char* src = bytes + t * NB;
         static_for<0, NW>([&](auto K) { w[K] = 0; });
         static_for<0, NB>([&](auto B) {

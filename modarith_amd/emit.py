@@ -187,6 +187,20 @@ def eval_chain(prog, x: int, p: int) -> int:
 
 
 MAX_GENERATED_LIMBS = 16  # generator mode (modarith_amd.generate): limbs stay in VGPRs; the widest built-in field has 13
+# ... and at word length 32 (modarith_amd.generate.generate_w32): 18 limbs of 29 bits hold every prime up to 521 bits and the 18-limb
+# named moduli (NIST521, PM512, GM512).  The one-element streaming kernels of the 22- and 26-limb units (SIDH610, SIDH751) have not
+# been shown free of scratch, so the cap stays here (docs/kernels_field.md 4.5)
+MAX_GENERATED_LIMBS_W32 = 18
+
+
+def w32_ept_max(nlimbs: int) -> int:
+    """MA_W32_EPT_MAX of a generated 32-bit unit: the widest elements-per-lane at which no streaming kernel (k_binary, k_unary, k_mli)
+    of a field of that many limbs has scratch or accumulation registers.  From cross-compiling for gfx950 (docs/kernels_field.md
+    4.5): four elements per lane are clean up to 16 limbs (163 VGPRs for the 16-limb modmul); at 18 limbs the four-element modmul
+    takes 255 VGPRs and accumulation registers, the two-element one 169 VGPRs."""
+    return 4 if nlimbs <= 16 else 2
+
+
 MAX_UNROLLED_MULS = 24   # beyond this the progenitor is a square-and-multiply loop (general primes)
 
 
@@ -347,7 +361,10 @@ def chain_ok(fp: FieldParams) -> bool:
     return c + words + s0 + (1 << R) < (1 << 64)
 
 
-def header_text(fp: FieldParams) -> str:
+def header_text(fp: FieldParams, generated: bool = False) -> str:
+    """the parameter struct.  generated=True (word length 32 only, modarith_amd.generate.generate_w32): the struct also carries the
+    driver's verdict on the shared inversion, INV_CLOSED (params.w32_inv_closure; csrc/capi_w32.inc inv_closed_of) -- the structs of
+    the built-in primes, whose closure is shown by hand in csrc/kernels.h, do not have the member"""
     N = fp.nlimbs
     prog = addition_chain(fp.pe)
     sq, mu = chain_cost(prog)
@@ -396,6 +413,13 @@ def header_text(fp: FieldParams) -> str:
     L.append(_switch("pp_sgn", "int", [t[1] for t in fp.pp], str))
     L.append(_switch("pp_val", "unsigned long long", [t[2] for t in fp.pp], _hexu))
     L.append(_switch("roi", "unsigned long long", fp.roi, _hexu))
+    if generated and fp.wl == 32:
+        from .params import w32_inv_closure
+        c = w32_inv_closure(fp)
+        L.append("    // shared inversion (kernels.h k_inv_simul): closure of \"digit form below 2^(Nbits+1)\" under this prime's products, params.w32_inv_closure: "
+                 + ("largest column sum < 2^%.2f, carry into the unmasked limb < 2^%d, top limb below 2^%d" % (c["column_bits"], c["slack"].bit_length(), c["topb"])
+                    if c["closed"] else "NOT shown (%s): one inversion per element" % c["why"]))
+        L.append("    static constexpr bool INV_CLOSED = %s;" % ("true" if c["closed"] else "false"))
     tp = trailing_plan(fp.pe)
     if tp is not None:
         L.append("    // progenitor for PE = %s = A*2^r + (2^r - 1), r = %d, A = %s: rolled doubling ladder, %d squarings + %d multiplications"
@@ -710,14 +734,16 @@ def field_shim_text(fp: FieldParams, tag: str = None) -> str:
 
 def _field_shim_text_w32(fp: FieldParams) -> str:
     """include/field_<PRIME>_w32.h: the same paste marker for the 32-bit word form -- the macro block of `pseudo.py 32` / `monty.py 32`
-    and the 32 names mapped onto the <fn>_<PRIME>_w32_ct entry points of include/modarith_amd_w32.h"""
+    and the 32 names mapped onto the <fn>_<PRIME>_w32_ct entry points of include/modarith_amd_w32.h (a generated field: declared
+    here with MODARITH_AMD_DECLARE_W32, defined by its plug-in)"""
     tag = "%s_w32" % fp.name
+    builtin = fp.name in W32_PRIMES
     L = ["/* include/field_%s.h -- EMITTED by modarith_amd/emit.py field_shim_text(); do not edit." % tag,
          " *",
          " * The 32-bit word form of field_%s.h (Wordlength 32: spint = uint32_t, dpint = uint64_t, the limbs of the reference's" % fp.name,
          " * `%s 32 %s` and of simd/%s's field.cu).  Put  #include \"field_%s.h\"  where the" % (
              "monty.py" if fp.montgomery else "pseudo.py", fp.name, "monty_cuda.py" if fp.montgomery else "pseudo_cuda.py", tag),
-         " * reference's templates say \"paste field.c here\" and link libmodarith_amd.so: modmul(a, b, c) ... then run on the GPU one",
+         " * reference's templates say \"paste field.c here\" and link libmodarith_amd.so%s: modmul(a, b, c) ... then run on the GPU one" % ("" if builtin else " and the field's plug-in"),
          " * element at a time (host pointers, the reference's signatures and aliasing rules; throughput comes from the",
          " * <fn>_%s_batch entry points of modarith_amd_w32.h)." % tag,
          " * prime %s = %s, %s" % (fp.name, hex(fp.p), "monty.py form" if fp.montgomery else "pseudo.py form"),
@@ -726,7 +752,7 @@ def _field_shim_text_w32(fp: FieldParams) -> str:
          "#define MODARITH_AMD_FIELD_%s_H" % tag.upper(),
          "#include <stdio.h>",
          "#include <stdint.h>",
-         '#include "modarith_amd_w32.h"',
+         '#include "modarith_amd_w32.h"'] + ([] if builtin else ["MODARITH_AMD_DECLARE_W32(%s)" % fp.name]) + [
          "",
          "#define sspint int32_t",
          "#define spint uint32_t",
@@ -740,15 +766,25 @@ def _field_shim_text_w32(fp: FieldParams) -> str:
          ""]
     if fp.montgomery:
         L.append("#define MONTGOMERY")
-        L.append("#define %s" % fp.name.upper())
+        if fp.name[0].isalpha():
+            L.append("#define %s" % fp.name.upper())
         if fp.trin > 0:
             L.append("#define MULBYINT")
     else:
-        L += ["#define MERSENNE", "#define MULBYINT", "#define %s" % fp.name]
+        L += ["#define MERSENNE", "#define MULBYINT"] + (["#define %s" % fp.name] if fp.name[0].isalpha() else [])
     L.append("")
     L += ["#define %s %s_%s_ct" % (fn, fn, tag) for fn in FIELD_C_NAMES]
     L += ["", "#endif", ""]
     return "\n".join(L)
+
+
+def capi_unit_text_w32(tag: str, nlimbs: int) -> str:
+    """translation unit of a generated field at word length 32: the three lines of csrc/capi_X25519_w32.hip over the generated struct,
+    and the widest streaming kernel its limb count allows (w32_ept_max)"""
+    return ("// GENERATED by modarith_amd/emit.py -- do not edit.\n"
+            "// C-ABI entry points of the 32-bit word form of %s (<fn>_%s_w32_batch / <fn>_%s_w32_ct); body: capi_w32.inc\n"
+            '#include "params_%s_w32.h"\n#define MA_P ma32::P_%s_W32\n#define MA_NAME %s\n#define MA_W32_EPT_MAX %d\n#include "capi_w32.inc"\n'
+            % (tag, tag, tag, tag, tag, tag, w32_ept_max(nlimbs)))
 
 
 def emit_field_shims(primes=CORE_PRIMES, out_dir: str = INCLUDE_DIR) -> List[str]:

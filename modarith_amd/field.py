@@ -71,7 +71,8 @@ class Field:
     Every method ACCEPTS both forms; `to_flat` / `to_tiled` convert; `creates_tiled(n)` tells which one n gets.
 
     Word length: `Field(prime, wl=32)` is the 32-bit word form of X25519, NIST256 and X448 (include/modarith_amd_w32.h: the limbs of
-    the reference's `pseudo.py 32` / `monty.py 32`, 9 x 29, 9 x 29 and 16 x 28 bits) on torch.int32 tensors of the same shapes.  It has
+    the reference's `pseudo.py 32` / `monty.py 32`, 9 x 29, 9 x 29 and 16 x 28 bits) on torch.int32 tensors of the same shapes, or of
+    a field generated at that word length (`Field.generate(prime, wl=32)`, modarith_amd.generate.generate_w32; up to 18 limbs).  It has
     every method of the 64-bit form except modmuls, the _lazy forms and time_protocol (NotImplementedError); modinv shares one
     inversion between up to 64 elements of a large batch as the 64-bit form does (same words as one inversion per element), and
     modarith_amd.fuse.Chain(prime, name, wl=32) fuses sequences of calls on such batches.  wl=64 is the default."""
@@ -86,10 +87,22 @@ class Field:
         self.wl = wl
         # the container of a limb (the limbs are unsigned), its numpy view, and what the entry points of this word length are called
         self.dtype, self._np, self._sfx = (torch.int64, np.uint64, "") if wl == 64 else (torch.int32, np.uint32, "_w32")
-        if wl == 32:
-            if prime not in _lib.W32_PRIMES:
-                raise ValueError("the 32-bit word form is built for %s (got %r); every other field is 64-bit only" % (", ".join(_lib.W32_PRIMES), prime))
+        if wl == 32 and prime in _lib.W32_PRIMES:
             self.params: FieldParams = derive(prime, wl=32)
+        elif wl == 32:
+            # a field made by generate_w32 (modarith_amd.generate): its kernels live in a plug-in of their own, libmodarith_amd_<TAG>_w32.so
+            from . import generate as _gen
+            if not os.path.exists(_gen.plugin_path(prime, wl=32)) and (prime[:1].isdigit() or "=" in prime):
+                try:
+                    prime = _gen.resolve(prime, wl=32).name
+                except _gen.GenerateError:
+                    pass
+            if not os.path.exists(_gen.plugin_path(prime, wl=32)):
+                raise ValueError("the 32-bit word form is built for %s and generated for %s (got %r): generate it with Field.generate(..., wl=32) "
+                                 "or `python -m modarith_amd.generate w32 <prime>`"
+                                 % (", ".join(_lib.W32_PRIMES), ", ".join(m["tag"] for m in _gen.installed(wl=32)) or "no other field yet", prime))
+            self.flib = _lib.load_plugin(prime, wl=32)
+            self.params = _gen.params_of_plugin(prime, wl=32)
         elif prime in _lib.PRIMES:
             self.params: FieldParams = derive(prime)
         else:
@@ -126,8 +139,11 @@ class Field:
     def generate(cls, prime: str, device: Optional[torch.device] = None, tile: Optional[int] = None, **kw) -> "Field":
         """the generator mode in one call: `Field.generate("2**251-9")` is `python pseudo.py 64 2**251-9` followed by loading
         what it built -- constants derived, kernels compiled for the prime (about ten seconds, reused afterwards), field bound.
-        Keywords as modarith_amd.generate.generate (family=, name=, radix=, force=)."""
+        Keywords as modarith_amd.generate.generate (family=, name=, radix=, force=).  wl=32: generate_w32, the 32-bit word form
+        (`python pseudo.py 32 ...`), bound as Field(tag, wl=32)."""
         from . import generate as _gen
+        if kw.pop("wl", 64) == 32:
+            return cls(_gen.generate_w32(prime, **kw).tag, device, tile, wl=32)
         return cls(_gen.generate(prime, **kw).tag, device, tile)
 
     # ------------------------------------------------------------------ buffers

@@ -88,11 +88,16 @@ class Chain:
             raise ValueError("word length must be 64 or 32 (got %r)" % (wl,))
         self.wl = wl
         if wl == 32:
-            if prime not in _lib.W32_PRIMES:
-                raise ValueError("the 32-bit word form is built for %s (got %r); every other field is 64-bit only" % (", ".join(_lib.W32_PRIMES), prime))
-            from .params import derive
-            self.params = derive(prime, wl=32)
-            self.builtin = True
+            if prime in _lib.W32_PRIMES:
+                from .params import derive
+                self.params = derive(prime, wl=32)
+                self.builtin = True
+            elif os.path.exists(_gen.plugin_path(prime, wl=32)):
+                self.params = _gen.params_of_plugin(prime, wl=32)      # a field of generate_w32: params_<TAG>_w32.h next to its plug-in
+                self.builtin = False
+            else:
+                raise ValueError("the 32-bit word form is built for %s (got %r) and generated for what `python -m modarith_amd.generate w32 <prime>` "
+                                 "has made; every other field is 64-bit only" % (", ".join(_lib.W32_PRIMES), prime))
         elif prime in _lib.PRIMES:
             from .params import derive
             self.params = derive(prime)
@@ -260,12 +265,14 @@ class Chain:
         cap = 1 if heavy else (ept or self.default_ept())
         if cap not in (1, 2, 4):
             raise ValueError("elements per lane at word length 32: 1, 2 or 4")
+        if not self.builtin:
+            cap = min(cap, emit.w32_ept_max(self.params.nlimbs))       # (the width a generated field's limb count leaves in registers)
         block = block or W32_BLOCK_DEFAULT
         if block not in (64, 128, 256):
             raise ValueError("workgroup size: 64, 128 or 256")
         args = ", ".join(["v%d[E]" % i for i in range(nv)] + ["s%d[E]" % k for k in range(self.nsel)])
         L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s, 32-bit word form: %d inputs, %d operations, %d outputs." % (self.name, P, self.nin, len(self.ops), len(self.outs)),
-             '#include "w32_%s.h"' % P, '#include "modarith_amd_w32.h"', '#include "capi_common.h"', '#include "kernels32.h"', "",
+             '#include "%s"' % ("w32_%s.h" % P if self.builtin else "params_%s_w32.h" % P), '#include "modarith_amd_w32.h"', '#include "capi_common.h"', '#include "kernels32.h"', "",
              "namespace {", "using namespace ma32;", "using ma::check_launch;", "using ma::grid_for;", "using ma::set_error;", "using P = ma32::P_%s_W32;" % P,
              "constexpr int NIN = %d, NOUT = %d, NSEL = %d;" % (self.nin, len(self.outs), self.nsel),
              "constexpr bool HEAVY = %s;   // an inversion, a progenitor or a square root in the chain: one element per lane" % ("true" if heavy else "false"),

@@ -4,6 +4,7 @@
   python -m modarith_amd.generate 64 BP256=0xa9fb57db...5377 --monty
   python -m modarith_amd.generate 64 2**251-9 --time        # ... and run the time.c protocol on the GPU, as the generators do last
   python -m modarith_amd.generate curve NIST224 weierstrass NIST224 -3 0xb405...ffb4 0xffff...2a3d 0xb70e...1d21 0xbd37...7e34
+  python -m modarith_amd.generate w32 BP256=0xa9fb57db...5377      # the same field on uint32_t limbs (`monty.py 32 ...`): generate_w32()
   python -m modarith_amd.generate --list
 
 This is the counterpart of `python pseudo.py 64 <prime>` / `python monty.py 64 <prime>` (pseudo.py:1461-1473,
@@ -17,8 +18,11 @@ libmodarith_amd.so (launch geometry, error text, staging buffers); `Field("<TAG>
 
 Naming follows the generators' decoration rule (pseudo.py:1940-1944, monty.py:2510-2520): a named prime keeps its
 name; an unnamed pseudo-Mersenne 2^n - m is tagged `<n><m>` ("25519"); any other unnamed modulus must be given a
-name (`NAME=<expression>` or `name=`), as monty.py insists ("Modulus must have a name").  Only 64-bit words are
-built: the MI355X kernels hold u64 limbs (SURVEY 8 sizes); 16 / 32 are refused with the reason.
+name (`NAME=<expression>` or `name=`), as monty.py insists ("Modulus must have a name").  generate() builds 64-bit words
+(u64 limbs, SURVEY 8 sizes) and refuses 16 / 32 with the reason; the 32-bit word form -- the limbs of the reference's `pseudo.py 32` /
+`monty.py 32` and of its CUDA generators -- is generate_w32() / the verb `w32`: the same resolution, tags and refusals at word
+length 32, a plug-in `libmodarith_amd_<TAG>_w32.so` over csrc/capi_w32.inc that exports what MODARITH_AMD_DECLARE_W32(<TAG>) of
+include/modarith_amd_w32.h declares, next to (and independent of) the 64-bit plug-in of the same tag; `Field("<TAG>", wl=32)` loads it.
 
 There is no CPU path here either: the plug-in contains GPU kernels only, and a missing hipcc is an error.
 """
@@ -34,7 +38,7 @@ from dataclasses import dataclass
 from typing import List, Optional
 
 from . import emit
-from .params import NAMED, FieldParams, derive_monty, derive_pseudo
+from .params import NAMED, RADIX_32, FieldParams, derive_monty, derive_pseudo
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PLUGIN_DIR = os.environ.get("MA_PLUGIN_DIR", os.path.join(HERE, "plugins"))
@@ -46,6 +50,14 @@ _TAG_RE = re.compile(r"^[A-Za-z0-9][A-Za-z0-9_]*$")
 # prime (brainpoolP256r1) in full Montgomery form, and monty.py's PM shortcut for an unnamed 2^n - m
 EXAMPLES = (("2**251-9", "pseudo"), ("2**130-5", "pseudo"),
             ("BP256=0xa9fb57dba1eea9bc3e660a909d838d726e3bf623d52620282013481d1f6e5377", "monty"), ("M2519=2**251-9", "monty"))
+
+
+# the 32-bit examples (tests/golden/field_w32gen_<TAG>.json.xz: what `pseudo.py 32` / `monty.py 32` emit for them), one per class: an
+# unnamed pseudo-Mersenne (9 x 28), the smallest (5 x 26), full Montgomery with ndash != 1 and a Barrett modmli, negative prime limbs
+# (14 x 28), a radix override, 18 limbs (the reduced launch width), a group order, and monty.py's form of 2^251 - 9
+EXAMPLES_W32 = (("2**251-9", "pseudo"), ("2**130-5", "pseudo"),
+                ("BP256=0xa9fb57dba1eea9bc3e660a909d838d726e3bf623d52620282013481d1f6e5377", "monty"), ("NIST384", None), ("GM240", None),
+                ("PM512", None), ("Q25519=00" + str(NAMED["ED25519Q"][0]), "monty"), ("M2519=2**251-9", "monty"))
 
 
 class GenerateError(ValueError):
@@ -72,13 +84,18 @@ def _evaluate(expr: str) -> int:
     return int(eval(expr, {"__builtins__": {}}))
 
 
-def resolve(prime: str, family: Optional[str] = None, name: Optional[str] = None, radix: Optional[int] = None) -> FieldParams:
-    """prime (a name of modarith_amd.params.NAMED, an expression, or NAME=expression) -> FieldParams with .name = TAG"""
+def resolve(prime: str, family: Optional[str] = None, name: Optional[str] = None, radix: Optional[int] = None, wl: int = 64) -> FieldParams:
+    """prime (a name of modarith_amd.params.NAMED, an expression, or NAME=expression) -> FieldParams with .name = TAG, at word length wl"""
     if "=" in prime and name is None:
         name, prime = prime.split("=", 1)
     if prime in NAMED:
         p, fam = NAMED[prime]
         name = name or prime
+        if wl == 32:
+            if radix is None:
+                radix = RADIX_32.get(prime)
+            if family is None and fam == "pseudo":
+                fam = None                # (a named pseudo-Mersenne that does not fit this word length falls back, as params.derive does)
         family = family or fam
     else:
         p = _evaluate(prime)
@@ -86,13 +103,13 @@ def resolve(prime: str, family: Optional[str] = None, name: Optional[str] = None
     fp = None
     if family in (None, "pseudo"):
         try:
-            fp = derive_pseudo(name or "_", p, radix)
+            fp = derive_pseudo(name or "_", p, radix, wl)
         except ValueError as e:
             if family == "pseudo":
                 raise GenerateError("%s (pseudo.py:1563-1592)" % e) from None
     if fp is None:
         try:
-            fp = derive_monty(name or "_", p, radix)
+            fp = derive_monty(name or "_", p, radix, wl)
         except ValueError as e:
             raise GenerateError("%s (monty.py:2131-2230)" % e) from None
     if name is None:
@@ -102,6 +119,9 @@ def resolve(prime: str, family: Optional[str] = None, name: Optional[str] = None
             raise GenerateError("Modulus must have a name - unable to make one for you (monty.py:2517-2519): pass NAME=<expression>")
     if not _TAG_RE.match(name):
         raise GenerateError("%r cannot be part of a C identifier" % (name,))
+    if name.lower().endswith("_w32"):
+        # libmodarith_amd_<TAG>_w32.so / <TAG>_w32.json / <fn>_<TAG>_w32_batch are the names of the 32-bit plug-in of <TAG>
+        raise GenerateError("%r: a tag cannot end in _w32, the suffix of the 32-bit word form's files and symbols" % (name,))
     fp.name = name
     return fp
 
@@ -119,8 +139,8 @@ def _key(fp: FieldParams, tag: str) -> str:
     return h.hexdigest()
 
 
-def plugin_path(tag: str, plugin_dir: Optional[str] = None) -> str:
-    return os.path.join(plugin_dir or PLUGIN_DIR, "libmodarith_amd_%s.so" % tag)
+def plugin_path(tag: str, plugin_dir: Optional[str] = None, wl: int = 64) -> str:
+    return os.path.join(plugin_dir or PLUGIN_DIR, "libmodarith_amd_%s%s.so" % (tag, "" if wl == 64 else "_w32"))
 
 
 def generate(prime: str, wl: int = 64, family: Optional[str] = None, name: Optional[str] = None, radix: Optional[int] = None,
@@ -128,8 +148,8 @@ def generate(prime: str, wl: int = 64, family: Optional[str] = None, name: Optio
     """derive the constants of `prime`, emit them, compile the kernels for it; returns the plug-in to load.
     An existing plug-in is reused when neither the constants nor any kernel source it was compiled from have changed."""
     if wl != 64:
-        raise GenerateError("the generator mode builds 64-bit words only (u64 limbs, 128-bit column sums); the 32-bit form exists for the "
-                            "built-in X25519, NIST256 and X448 (Field(P, wl=32), include/modarith_amd_w32.h), the 16-bit form not at all")
+        raise GenerateError("generate() builds 64-bit words only (u64 limbs, 128-bit column sums); the 32-bit form is generate_w32() / "
+                            "`python -m modarith_amd.generate w32 <prime>` (include/modarith_amd_w32.h), the 16-bit form does not exist")
     fp = resolve(prime, family, name, radix)
     tag = fp.name
     from . import _lib
@@ -172,6 +192,60 @@ def generate(prime: str, wl: int = 64, family: Optional[str] = None, name: Optio
                            "-Wl,-rpath,$ORIGIN/" + rel, "-Wl,-rpath," + HERE])
     with open(meta + tmp, "w") as f:
         json.dump({"tag": tag, "prime": prime, "p": hex(fp.p), "family": fp.family, "radix": fp.radix, "nlimbs": fp.nlimbs, "hash": key}, f, indent=1)
+    os.replace(obj + tmp, obj)
+    os.replace(lib + tmp, lib)
+    os.replace(meta + tmp, meta)
+    return Generated(tag, lib, fp, True)
+
+
+def generate_w32(prime: str, family: Optional[str] = None, name: Optional[str] = None, radix: Optional[int] = None,
+                 plugin_dir: Optional[str] = None, force: bool = False, verbose: bool = False) -> Generated:
+    """generate() at word length 32: `python pseudo.py 32 <prime>` / `python monty.py 32 <prime>`.  Emits, next to each other in the
+    plug-in directory, params_<TAG>_w32.h (emit.header_text: struct ma32::P_<TAG>_W32, with the driver's verdict on the shared
+    inversion), capi_<TAG>_w32.hip (three lines over csrc/capi_w32.inc and the launch width the limb count allows), field_<TAG>_w32.h
+    (the paste-marker shim), libmodarith_amd_<TAG>_w32.so and the metadata <TAG>_w32.json ("wl": 32).  Caching, atomic renames and
+    linking as generate(); the 64-bit plug-in of the same tag is neither needed nor touched.  X25519, NIST256 and X448 are built in."""
+    fp = resolve(prime, family, name, radix, wl=32)
+    tag = fp.name
+    from . import _lib
+    if tag in _lib.W32_PRIMES and NAMED[tag][0] == fp.p and (family is None or NAMED[tag][1] == fp.family) and radix is None:
+        return Generated(tag, _lib.LIB_PATH, fp, False)         # a built-in prime: nothing to generate
+    if tag in _lib.W32_PRIMES:
+        raise GenerateError("%s names a built-in field with other constants; choose another name" % tag)
+    if fp.nlimbs > emit.MAX_GENERATED_LIMBS_W32:
+        raise GenerateError("%d limbs of %d bits: the 32-bit kernels keep every operand in registers and are built for at most %d limbs "
+                            "(no streaming kernel beyond that has been shown free of scratch)" % (fp.nlimbs, fp.radix, emit.MAX_GENERATED_LIMBS_W32))
+    d = plugin_dir or PLUGIN_DIR
+    os.makedirs(d, exist_ok=True)
+    stem = "%s_w32" % tag
+    hdr, unit = os.path.join(d, "params_%s.h" % stem), os.path.join(d, "capi_%s.hip" % stem)
+    obj, lib, meta = os.path.join(d, "capi_%s.o" % stem), plugin_path(tag, d, 32), os.path.join(d, "%s.json" % stem)
+    hdr_text, unit_text = emit.header_text(fp, generated=True), emit.capi_unit_text_w32(tag, fp.nlimbs)
+    from .build import ARCH, FLAGS, HIPCC, _stamp
+    key = hashlib.sha256((" ".join(FLAGS) + "\n" + hdr_text + "\n" + unit_text + "\n" + _stamp()).encode()).hexdigest()
+    emit._write(hdr, hdr_text)
+    emit._write(os.path.join(d, "field_%s.h" % stem), emit.field_shim_text(fp))
+    emit._write(unit, unit_text)
+    if not force and os.path.exists(lib) and os.path.exists(meta):
+        try:
+            if json.load(open(meta)).get("hash") == key:
+                return Generated(tag, lib, fp, False)
+        except (ValueError, OSError):
+            pass
+    if not os.path.exists(HIPCC):
+        raise GenerateError("%s not found: generating a field needs the ROCm compiler (there is no CPU path)" % HIPCC)
+    main = os.path.join(HERE, "libmodarith_amd.so")
+    if not os.path.exists(main):
+        raise GenerateError("%s is missing: build it first (python -m modarith_amd.build); plug-ins link against it" % main)
+    if verbose:
+        print("[modarith_amd] hipcc %s -> %s" % (os.path.basename(unit), os.path.basename(lib)), flush=True)
+    tmp = ".%d.tmp" % os.getpid()
+    subprocess.run([HIPCC] + _flags() + ["-c", unit, "-o", obj + tmp], check=True, timeout=int(os.environ.get("MA_BUILD_TIMEOUT", "1500")))
+    subprocess.check_call([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib + tmp, obj + tmp, "-L", HERE, "-l:libmodarith_amd.so",
+                           "-Wl,-rpath,$ORIGIN/" + os.path.relpath(HERE, d), "-Wl,-rpath," + HERE])
+    with open(meta + tmp, "w") as f:
+        json.dump({"tag": tag, "wl": 32, "prime": prime, "p": hex(fp.p), "family": fp.family, "radix": fp.radix, "nlimbs": fp.nlimbs,
+                   "ept_max": emit.w32_ept_max(fp.nlimbs), "hash": key}, f, indent=1)
     os.replace(obj + tmp, obj)
     os.replace(lib + tmp, lib)
     os.replace(meta + tmp, meta)
@@ -397,28 +471,28 @@ EXAMPLE_CURVES = (
 )
 
 
-def installed(plugin_dir: Optional[str] = None) -> List[dict]:
-    """metadata of every plug-in whose shared object is present"""
+def installed(plugin_dir: Optional[str] = None, wl: int = 64) -> List[dict]:
+    """metadata of every field plug-in of word length wl whose shared object is present (64: the default; 32: generate_w32's)"""
     d = plugin_dir or PLUGIN_DIR
     out = []
     if os.path.isdir(d):
         for f in sorted(os.listdir(d)):
-            if f.endswith(".json") and os.path.exists(plugin_path(f[:-5], d)):
+            if f.endswith(".json") and os.path.exists(plugin_path(f[:-5], d)):      # (<TAG>_w32.json sits next to libmodarith_amd_<TAG>_w32.so)
                 try:
                     m = json.load(open(os.path.join(d, f)))
                 except ValueError:
                     continue
-                if "tag" in m:                         # (the directory also holds the plug-ins of fused chains, modarith_amd/fuse.py)
+                if "tag" in m and m.get("wl", 64) == wl:      # (the directory also holds the plug-ins of fused chains, modarith_amd/fuse.py)
                     out.append(m)
     return out
 
 
-def params_of_plugin(tag: str, plugin_dir: Optional[str] = None) -> FieldParams:
+def params_of_plugin(tag: str, plugin_dir: Optional[str] = None, wl: int = 64) -> FieldParams:
     """FieldParams of an installed plug-in, re-derived from its recorded modulus / family / radix"""
     d = plugin_dir or PLUGIN_DIR
-    meta = json.load(open(os.path.join(d, "%s.json" % tag)))
+    meta = json.load(open(os.path.join(d, "%s%s.json" % (tag, "" if wl == 64 else "_w32"))))
     p = int(meta["p"], 16)
-    fp = (derive_pseudo if meta["family"] == "pseudo" else derive_monty)(tag, p, meta["radix"])
+    fp = (derive_pseudo if meta["family"] == "pseudo" else derive_monty)(tag, p, meta["radix"], wl)
     return fp
 
 
@@ -471,11 +545,42 @@ def time_report(tag: str, outer: int = 100000, lanes: int = 1 << 16) -> List[str
     return out
 
 
+def time_report_w32(tag: str, n: int = 1 << 20, launches: int = 10) -> List[str]:
+    """--time at word length 32.  The time.c chains (k_time) are not built at this word length (W32_ABSENT: time_protocol), so this
+    reports what the batched entry points do instead: elements per second of modmul, modsqr and modinv on n uniform elements, each the
+    median of `launches` single launches timed by device events after three warm-up launches (docs/measurement.md)."""
+    import statistics
+
+    import torch
+    from .field import Field
+    F = Field(tag, wl=32)
+    x, y, z = F.nres(F.uniform(n, array=1)), F.nres(F.uniform(n, array=2)), F.empty(n)
+    out = []
+    for leg, call in (("modmul", lambda: F.modmul(x, y, out=z)), ("modsqr", lambda: F.modsqr(x, out=z)), ("modinv", lambda: F.modinv(x, out=z))):
+        for _ in range(3):
+            call()
+        torch.cuda.synchronize(F.device)
+        ev = []
+        for _ in range(launches):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call()
+            e1.record()
+            ev.append((e0, e1))
+        torch.cuda.synchronize(F.device)
+        ms = statistics.median(e0.elapsed_time(e1) for e0, e1 in ev)
+        out.append("%s %.3g elements/s (%d elements, batched entry point, 32-bit words; median of %d launches by device events, %.3f ms)"
+                   % (leg, n / (ms * 1e-3), n, launches, ms))
+    return out
+
+
 def main(argv: List[str]) -> int:
     args = [a for a in argv if not a.startswith("--")]
     if "--list" in argv:
         for m in installed():
             print("%-12s %-6s %2d x %2d bits  %s" % (m["tag"], m["family"], m["nlimbs"], m["radix"], m["prime"]))
+        for m in installed(wl=32):
+            print("%-12s %-6s %2d x %2d bits  %s   (32-bit words)" % (m["tag"], m["family"], m["nlimbs"], m["radix"], m["prime"]))
         for m in installed_curves():
             print("%-12s %-11s over %-8s a = %d, b = %s" % (m["curve"], m["kind"], m["field"], m["a"], m["b"]))
         d = PLUGIN_DIR
@@ -513,9 +618,27 @@ def main(argv: List[str]) -> int:
     if len(args) != 2:
         print("Syntax error")
         print("Valid syntax - python -m modarith_amd.generate <word length> <prime> OR <prime name> OR <name>=<prime> [--pseudo|--monty] [--force] [--time[=outer]]")
+        print("               python -m modarith_amd.generate w32 <prime> ... (the 32-bit word form)")
         print("For example - python -m modarith_amd.generate 64 2**255-19")
         return 2
     fam = "pseudo" if "--pseudo" in argv else "monty" if "--monty" in argv else None
+    if args[0] == "w32":
+        # python -m modarith_amd.generate w32 <prime> [--monty|--pseudo] [--time]: the reference's `pseudo.py 32 <prime>` / `monty.py 32 <prime>`
+        try:
+            g = generate_w32(args[1], family=fam, force="--force" in argv, verbose=True)
+        except GenerateError as e:
+            print(e)
+            return 2
+        print(report(g.params))
+        from .params import w32_inv_closure
+        c = w32_inv_closure(g.params)
+        print("launch width: at most %d elements per lane; shared inversion: %s" % (emit.w32_ept_max(g.params.nlimbs),
+              "closure shown (columns below 2^%.2f)" % c["column_bits"] if c["closed"] else "closure not shown (%s), one inversion per element" % c["why"]))
+        if any(a == "--time" or a.startswith("--time=") for a in argv):
+            for line in time_report_w32(g.tag):
+                print(line)
+        print("%s %s: C-ABI <fn>_%s_w32_ct / <fn>_%s_w32_batch (MODARITH_AMD_DECLARE_W32(%s)); Field(%r, wl=32)" % ("built" if g.built else "up to date:", g.lib, g.tag, g.tag, g.tag, g.tag))
+        return 0
     try:
         g = generate(args[1], int(args[0]), family=fam, force="--force" in argv, verbose=True)
     except GenerateError as e:

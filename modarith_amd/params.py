@@ -86,6 +86,10 @@ NAMED = {
 # per-name radix choices the generators hard-wire for 64-bit words (monty.py:2002-2037, `if WL==64: base=...`)
 RADIX_64 = {"GM240": 61, "GM360": 57, "GM480": 60, "GM384": 62, "GM512": 58, "MFP4": 52, "MFP7": 52, "MFP1973": 52, "PM512M": 58}
 
+# ... and for 32-bit words (monty.py:2000-2037 `if WL==32: base=29` for the GM primes -- GM480 and GM512 get 29 from the default rule
+# too --, pseudo.py:1507-1510 for NIST521): without them the default rule gives GM240 27, GM360 and GM384 28 bits
+RADIX_32 = {"GM240": 29, "GM360": 29, "GM480": 29, "GM384": 29, "GM512": 29, "NIST521": 29}
+
 # keys of NAMED that are not the generators' own spelling
 REFERENCE_NAME = {"SECP256K1M": "SECP256K1", "PM383M": "PM383", "PM266M": "PM266", "PM336M": "PM336", "C41417M": "C41417", "PM512M": "PM512",
                   "M607": "2**607-1"}
@@ -342,6 +346,12 @@ def derive(name: str, family: Optional[str] = None, radix: Optional[int] = None,
         fam = "pseudo" if ((1 << n) - p) < (1 << 32) else "monty"
     if radix is None and fam == "monty" and wl == 64:
         radix = RADIX_64.get(name)
+    if radix is None and wl == 32:
+        radix = RADIX_32.get(name)
+    if wl == 32 and fam == "pseudo" and family is None and name in NAMED and ((1 << p.bit_length()) - p) >> _pm_radix(p.bit_length(), 32):
+        # a named prime whose 2^n - m does not fit a limb of this word length is not a pseudo-Mersenne there: pseudo.py names
+        # SECP256K1 for 64-bit words only (pseudo.py:1547 `and WL==64`), `monty.py 32 SECP256K1` builds it (monty.py:2061)
+        fam = "monty"
     return derive_pseudo(name, p, radix, wl) if fam == "pseudo" else derive_monty(name, p, radix, wl)
 
 
@@ -360,3 +370,139 @@ def w32_inv_in_contract(fp: FieldParams, limbs):
         raise ValueError("expected %d limbs" % N)
     ok = ((a[:N - 1] >> np.uint64(R)) == 0).all(axis=0) & ((a[N - 1] >> np.uint64(topb)) == 0)
     return bool(ok) if a.ndim == 1 else ok
+
+
+def w32_inv_closure(fp: FieldParams) -> dict:
+    """The proof that goes with w32_inv_in_contract, computed: is "digit form below 2^(Nbits+1)" closed under the products of the
+    32-bit word form of this prime?  It is what the comment above inv_in_contract in csrc/kernels.h works out by hand for X25519,
+    NIST256 and X448, as interval arithmetic over the statements of csrc/field.h at MA_WL = 32 (pm_modmul + pm_second_pass,
+    monty_mul + monty_reduce + monty_digit), which are identities over the integers as long as no 64-bit column and no 32-bit word
+    wraps; so only sizes are shown.  Operand set W: limbs 0..N-2 at most 2^Radix - 1 -- plus `slack` on the one limb a
+    pseudo-Mersenne second pass leaves unmasked (limb 1, limb 2 with carry_on) --, top limb below 2^TOPB, TOPB = Nbits + 1 -
+    Radix (N-1).  Shown, with both operands anywhere in W:
+      * products per column, with the top-limb slack and the unmasked limb;
+      * pseudo-Mersenne: the fold by mm -- the pre-multiplied limbs of the EPM form fit a word; the overflow form's carried high
+        part fits a word and lo + hi does not wrap; or mm times the folded sum fits the double word -- then the carries and the second
+        pass (its word or double-word form), whose carry into the unmasked limb must not exceed the slack assumed (the least fixed
+        point is taken) and whose output must stay below 2p;
+      * Montgomery: the digit-times-prime-limb terms (shifted digits for powers of two, one word for +-1 limbs, the scaled borrow of
+        monty.py's PM form), with the digit-times-p0 product where ndash != 1, the carries, and (a b + q p) / R < 2p for a, b below
+        2^(Nbits+1) -- which needs R >= 2^(Nbits+3) or so: three spare bits, or the virtual limb.
+    The squarings (pm_modsqr, monty_mul<true>) add the same products column by column -- twice the cross terms, `tot *= 2`, then the
+    square -- so every partial sum there is at most the column bound shown for the product of two operands of W.
+    -> {"closed": bool, "column": largest column sum found, "column_bits": its log2, "slack": carry into the unmasked limb,
+        "topb": TOPB, "hi": largest carried high part of the overflow form (0 elsewhere), "why": the first bound that failed or ""}.
+    closed = False is a statement about this proof, not about the prime: such a field keeps one inversion per element."""
+    import math
+    if fp.wl != 32:
+        raise ValueError("the closure belongs to the 32-bit word form")
+    N, R, n, p = fp.nlimbs, fp.radix, fp.n, fp.p
+    Q, W64, W32 = 1 << R, 1 << 64, 1 << 32
+    mask = Q - 1
+    topb = n + 1 - R * (N - 1)
+    out = {"closed": False, "column": 0, "column_bits": 0.0, "slack": 0, "topb": topb, "hi": 0, "why": ""}
+
+    def fail(why):
+        out["why"] = why
+        return out
+
+    def done(col, slack=0, hi=0):
+        out.update(closed=True, column=col, column_bits=round(math.log2(col), 2), slack=slack, hi=hi)
+        return out
+
+    if not (0 < topb <= 29 and R <= 29):
+        return fail("TOPB = %d, Radix = %d: the predicate is stated for at most 29 bits each" % (topb, R))
+    top = (1 << topb) - 1
+    if fp.family == "pseudo":
+        if fp.bad_overflow:
+            return fail("bad_overflow form")
+        k = 2 if fp.carry_on else 1
+        if k >= N - 1:
+            return fail("too few limbs")
+        slack = 0
+        for _ in range(8):
+            lim = [mask] * (N - 1) + [top]
+            lim[k] += slack
+            t = colmax = himax = hi_ov = 0
+            for row in range(N):
+                tt = sum(lim[j] * lim[N + row - j] for j in range(row + 1, N))
+                col = sum(lim[j] * lim[row - j] for j in range(row + 1))
+                if fp.epm:
+                    if max(lim[1:]) * fp.mm >= W32:
+                        return fail("a limb times mm leaves the word (EPM form)")
+                    t += tt * fp.mm
+                elif row < N - 1:
+                    if tt >= W64:
+                        return fail("folded column of row %d" % row)
+                    if fp.overflow:
+                        if row and mask + hi_ov >= W32:
+                            return fail("lo + hi wraps in row %d" % row)
+                        t += (mask + (hi_ov if row else 0)) * fp.mm
+                        hi_ov = tt >> R
+                        himax = max(himax, hi_ov)
+                        if hi_ov >= W32:
+                            return fail("carried high part of row %d leaves the word" % row)
+                    else:
+                        if tt * fp.mm >= W64:
+                            return fail("mm times the folded column of row %d" % row)
+                        t += tt * fp.mm
+                t += col
+                if fp.overflow and row == N - 1:
+                    t += hi_ov * fp.mm
+                if t >= W64:
+                    return fail("column %d" % row)
+                colmax = max(colmax, t)
+                t >>= R
+            # second pass: ut = m (2^xcess t + (v_top >> (Radix - xcess))), in a word (fred) or a double word
+            ut = (t << fp.xcess) + ((mask >> (R - fp.xcess)) if fp.xcess else 0)
+            ut *= fp.m
+            if ut >= (W32 if fp.fred else W64):
+                return fail("second pass: m (2^xcess t + top bits) leaves the %s" % ("word" if fp.fred else "double word"))
+            carry = ((mask + min(ut, mask)) >> R) + (ut >> R)
+            if fp.carry_on:                                    # (one more masked limb: the carry of limb 0 goes through limb 1)
+                carry = ((mask + min(carry, mask)) >> R) + (carry >> R)
+            if mask + slack + carry >= W32:
+                return fail("second pass: carry into limb %d" % k)
+            if carry <= slack:
+                value = ((1 << (n - R * (N - 1))) - 1 << (R * (N - 1))) + sum((mask + (carry if i == k else 0)) << (R * i) for i in range(N - 1))
+                if value >= 2 * p:
+                    return fail("product output not below 2p")
+                return done(colmax, slack, himax)
+            slack = carry
+        return fail("no fixed point for the unmasked limb")
+    # Montgomery
+    lim = [mask] * (N - 1) + [top]
+    lmax = N if fp.E else N - 1
+    ppw = list(fp.ppw) + [0] * (lmax + 1 - len(fp.ppw))
+    if fp.ndash != 1 and not fp.pm and ppw[0] <= 0:
+        return fail("full Montgomery reduction with a negative low limb")
+    ncol = 2 * N if fp.E else 2 * N - 1
+    neg = next((i for i, v in enumerate(ppw) if i > 0 and v == -1), 0)
+    t = colmax = 0
+    for c in range(ncol):
+        if neg and c > neg:
+            # monty_reduce's 32-bit scratch word of the columns past the negative limb: s = mask + (digits under +1 limbs) - (the digit
+            # under the -1 limb).  It must not wrap upwards (the subtraction takes at most the mask it starts from)
+            plus = sum(1 for l in range(1, lmax + 1) if ppw[l] == 1 and 0 <= c - l <= lmax and c - l < c)
+            if mask * (1 + plus) >= W32:
+                return fail("the scratch word of column %d: %d digits under +1 limbs on top of the mask" % (c, plus))
+        lo, hi = (0, c) if c < N else (c - (N - 1), N - 1)
+        t += sum(lim[j] * lim[c - j] for j in range(lo, hi + 1))
+        if fp.pm and c >= 1:
+            t += fp.m * mask
+        for l in range(1, lmax + 1):
+            j = c - l
+            if 0 <= j <= lmax and j < c and ppw[l]:
+                d = ppw[l]
+                t += mask * d if d > 1 else Q              # (+-1 limbs: one word below 2^Radix, or the borrow word)
+        if c <= lmax:
+            if fp.ndash != 1:
+                t += fp.m * Q if fp.pm else mask * ppw[0]
+        if t >= W64:
+            return fail("column %d" % c)
+        colmax = max(colmax, t)
+        t >>= R
+    a = (1 << (n + 1)) - 1
+    if a * a // fp.R + p >= 2 * p:
+        return fail("(a b + q p) / R is not below 2p for a, b below 2^(Nbits+1): R = 2^%d leaves %d spare bits" % (fp.R.bit_length() - 1, fp.R.bit_length() - 1 - n))
+    return done(colmax)
