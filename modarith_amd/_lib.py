@@ -264,27 +264,35 @@ def load_plugin(tag: str, path: str = None, wl: int = 64) -> ctypes.CDLL:
 _curve_plugins = {}
 
 
-def load_curve_plugin(name: str, path: str = None):
-    """Load the plug-in of a generated curve (modarith_amd.generate.generate_curve); returns (CDLL, Nlimbs, Nbytes)"""
+def load_curve_plugin(name: str, path: str = None, wl: int = 64):
+    """Load the plug-in of a generated curve (modarith_amd.generate.generate_curve); returns (CDLL, Nlimbs, Nbytes).  wl=32: the
+    plug-in of generate_curve(..., wl=32), whose entry points are ecn_<c>_w32_* (MODARITH_AMD_DECLARE_W32_CURVE)."""
     low = name.lower()
-    if low in _curve_plugins:
-        return _curve_plugins[low]
+    if wl not in (64, 32):
+        raise ValueError("word length must be 64 or 32")
+    key = low if wl == 64 else (low, 32, path)
+    if key in _curve_plugins:
+        return _curve_plugins[key]
     load()
     import json
     from .generate import PLUGIN_DIR, curve_plugin_path
-    path = path or curve_plugin_path(low)
-    meta = os.path.join(os.path.dirname(path), "curve_%s.json" % name.upper())
+    path = path or curve_plugin_path(low, wl=wl)
+    meta = os.path.join(os.path.dirname(path), "curve_%s%s.json" % (name.upper(), "" if wl == 64 else "_w32"))
     if not (os.path.exists(path) and os.path.exists(meta)):
         raise RuntimeError("modarith_amd: no plug-in for curve %r (%s) -- generate it with modarith_amd.generate.generate_curve(...). "
                            "There is no CPU fallback." % (name, path))
     m = json.load(open(meta))
     field = m["field"]
-    if field not in PRIMES:
-        load_plugin(field)                 # the curve's field is itself a plug-in
+    if wl == 64:
+        if field not in PRIMES:
+            load_plugin(field)                 # the curve's field is itself a plug-in
     lib = ctypes.CDLL(path)
-    _declare_curve(lib, low)
-    _curve_plugins[low] = (lib, m["nlimbs"], m["nbytes"])
-    return _curve_plugins[low]
+    if wl == 64:
+        _declare_curve(lib, low)
+    else:
+        _declare_curve(lib, low + "_w32", W32_ED_BATCH_FUNCS)      # (the curve plug-in carries its own kernels: the field's plug-in is needed by Field, not here)
+    _curve_plugins[key] = (lib, m["nlimbs"], m["nbytes"])
+    return _curve_plugins[key]
 
 
 class DeviceError(RuntimeError):

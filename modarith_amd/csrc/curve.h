@@ -115,10 +115,23 @@ struct CurveOps {
     struct Table {
         row_t* base;       // slab of this wave (table of mul, or first / second table of mul2): wave-uniform
         unsigned lane;     // 0..63
+        static constexpr bool REBORN = (MA_WL == 32 && N > 16);      // here() forms the lane number anew instead of reading `lane` (below)
         // here(): the lane offset as a value born at this access -- otherwise the row addresses (an entry of an 8- or 9-limb curve
         // spans 12-14 KB, beyond one base register's +-4 KB immediate range) are loop-invariant, get hoisted to the top of the
         // kernel and live (and spill) through the whole multiplication; recomputed they cost two instructions per access
+        // At 18 limbs of 32 bits (generated curves: NIST521, ED500) even the lane number does not keep a register through a 256-register
+        // multiplication: the allocator spills it and every table row of every lookup starts with a scratch load.  The kernels that
+        // use a Table run one wave per workgroup, so the lane number is the count of lanes below this one -- two instructions, no
+        // register held and nothing to spill.  (In assembly, volatile: the builtin is a pure function of nothing, so its value would be
+        // formed once at the top of the kernel, which is where this started.)
         MA_DEV unsigned here() const {
+#if MA_WL == 32 && defined(__HIP_DEVICE_COMPILE__)
+            if constexpr (REBORN) {
+                unsigned l;
+                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+                return l;
+            }
+#endif
             unsigned l = lane;
 #if defined(__HIP_DEVICE_COMPILE__)
             asm volatile("" : "+v"(l));
@@ -232,18 +245,24 @@ struct CurveOps {
         dg[(size_t)(2 * NB) * 64] = (signed char)c;
     }
 
+    // the digit of window i.  dg is the lane's column of the digit array -- or, where the lane number is formed anew at each use
+    // (Table::REBORN), the wave's array, and the column is chosen here: no LDS address lives through the multiplication either
+    static MA_DEV int digit(const signed char* dg, int i, const Table& W) {
+        if constexpr (Table::REBORN) return (int)dg[(size_t)i * 64 + W.here()];
+        else return (int)dg[(size_t)i * 64];
+    }
     // P = e*P, signed 4-bit fixed window (edwards.c:435-482).  dg = the recoded scalar (recode() above).  The table lookup of a
     // window comes after its four doublings (the order does not matter to either), so the looked-up point is not live across them.
     static MA_DEV void mul(const signed char* dg, Point& p, const Table& W) {
         build_table(p, W);
-        select((int)dg[(size_t)(2 * NB) * 64], W, p);
+        select(digit(dg, 2 * NB, W), W, p);
 #pragma unroll 1
         for (int i = 2 * NB - 1; i >= 0; i--) {
             i = scalar(i);
 #pragma unroll 1
             for (int r = 0; r < 4; r++) Crv::dbl(p);
             Point Q;
-            select((int)dg[(size_t)i * 64], W, Q);
+            select(digit(dg, i, W), W, Q);
             Crv::add(Q, p);
         }
     }
@@ -409,7 +428,7 @@ __global__ __launch_bounds__(64, (GUARD < 0 ? 2 : MA_MUL_WPS)) void k_ed_mul(con
     static_assert((size_t)4 * MA_MUL_WPS * 2 * E::NDIG * 64 <= (size_t)160 * 1024, "LDS budget of the resident scalar-multiplication grid");
     __shared__ signed char digs[E::NDIG * 64];
     const typename E::Table W{reinterpret_cast<typename E::row_t*>(ws) + (size_t)blockIdx.x * E::SLAB_WORDS, threadIdx.x};
-    signed char* dg = digs + threadIdx.x;
+    signed char* dg = digs + (E::Table::REBORN ? 0u : threadIdx.x);        // (REBORN: the wave's array, CurveOps::digit)
     // base: the wave's first element of this pass, wave-uniform (SGPRs); a lane's element index base + lane is formed where it is used
     // (W.here(): the lane number as a fresh value), so no 64-bit index or address stays in VGPRs across the multiplication
     for (size_t base = (size_t)blockIdx.x * 64; base < n; base += (size_t)gridDim.x * 64) {
@@ -420,7 +439,7 @@ __global__ __launch_bounds__(64, (GUARD < 0 ? 2 : MA_MUL_WPS)) void k_ed_mul(con
         {
             word_t ew[E::NW];
             load_be_record<typename E::P>(e, base + W.here(), ew);         // big-endian byte record -> little-endian words
-            E::recode(ew, dg);
+            E::recode(ew, dg + (E::Table::REBORN ? W.here() : 0u));
         }
         typename E::Point p;
         E::load(Pb, ld, base + W.here(), p);
@@ -505,9 +524,11 @@ enum { ED_ADD = 0, ED_SUB, ED_DBL, ED_NEG, ED_INF, ED_GEN, ED_COF, ED_AFFINE, ED
 // At 32-bit limbs two points and the temporaries of a formula are 100-250 registers before any product: with nothing but the workgroup
 // size to bound it the allocator spreads add / sub / dbl over 268-294 registers, accumulation registers included (one wave per SIMD).
 // Two waves per SIMD cap the kernel at 256 architectural registers -- except add / sub of the 16-limb field, which would then spill
-// 16-18 registers; those two stay unbounded (tools/spill_allowlist.json).  The 64-bit kernels keep the bound they always had.
+// 16-18 registers; those two stay unbounded (tools/spill_allowlist.json).  At 18 limbs (generated curves over 521- and 500-bit fields:
+// tools/w32_curve_gen_resources.json) the doubling alone would spill 52 registers under that cap and is left unbounded as well.
+// The 64-bit kernels keep the bound they always had.
 #if MA_WL == 32
-#define MA_ED_OP_BOUNDS __launch_bounds__(BLOCK, ((Crv::N > 9 && (OP == ED_ADD || OP == ED_SUB)) ? 1 : 2))
+#define MA_ED_OP_BOUNDS __launch_bounds__(BLOCK, (((Crv::N > 9 && (OP == ED_ADD || OP == ED_SUB)) || (Crv::N > 16 && OP == ED_DBL)) ? 1 : 2))
 #else
 #define MA_ED_OP_BOUNDS __launch_bounds__(BLOCK)
 #endif

@@ -27,24 +27,35 @@ class Edwards:
     Edwards ("ED25519", "ED448", "NUMS256E", "ED248", "ED376", "ED500") and short Weierstrass ("NIST256", "NIST384", "NIST521", "SECP256K1", "NUMS256W").  `Curve` is an alias.
 
     wl=32: the same API on the points of `curve.py 32 <CURVE>` -- torch.int32 tensors [3, Nlimbs, n] of 29- / 28-bit limbs (ED25519 and
-    NIST256: 9 limbs, ED448: 16; include/modarith_amd_w32_curve.h), the reference's limbs for every 32-bit limb pattern.  mul2 is the
+    NIST256: 9 limbs, ED448: 16; include/modarith_amd_w32_curve.h; any other curve -- the other eight of the table, or one's own -- as a
+    plug-in of modarith_amd.generate.generate_curve(..., wl=32)), the reference's limbs for every 32-bit limb pattern.  mul2 is the
     reference's own walk there (`exact` changes nothing); the fused byte-output forms are offered at word length 64 only."""
 
     W32 = ("ED25519", "NIST256", "ED448")       # curves built at word length 32
 
-    def __init__(self, curve: str, device: Optional[torch.device] = None, wl: int = 64):
+    def __init__(self, curve: str, device: Optional[torch.device] = None, wl: int = 64, plugin_dir: Optional[str] = None):
         self.name = curve.lower()
         if wl not in (64, 32):
             raise ValueError("wl must be 64 or 32")
         self.wl = wl
         self.dtype = torch.int64 if wl == 64 else torch.int32
         self._sym = self.name if wl == 64 else self.name + "_w32"      # ecn_<sym>_<fn>_batch
-        if wl == 32:
-            if curve.upper() not in self.W32:
-                raise ValueError("curve %r is not built at word length 32 (built there: %s)" % (curve, ", ".join(self.W32)))
+        self._plugin_dir = plugin_dir
+        if wl == 32 and curve.upper() in self.W32:
             self.lib = _lib.load()
             self.N, self.nbytes = _lib.W32_CURVES[self.name]
             self._field = None
+        elif wl == 32:
+            # a curve made by modarith_amd.generate.generate_curve(..., wl=32), the counterpart of `curve.py 32 <CURVE>` (plugin_dir: where
+            # it was generated, if not the default directory)
+            from . import generate as _gen
+            path = _gen.curve_plugin_path(self.name, plugin_dir, 32)
+            meta = next((m for m in _gen.installed_curves(plugin_dir, wl=32) if m["curve"].lower() == self.name), None)
+            if meta is None:
+                raise ValueError("curve %r is not built at word length 32 (built there: %s; generated: %s; see modarith_amd.generate.generate_curve(..., wl=32))"
+                                 % (curve, ", ".join(self.W32), ", ".join(m["curve"] for m in _gen.installed_curves(plugin_dir, wl=32)) or "none"))
+            self.lib, self.N, self.nbytes = _lib.load_curve_plugin(self.name, path, wl=32)
+            self._field = meta["field"]
         elif self.name in _lib.CURVES:
             self.lib = _lib.load()
             self.N, self.nbytes = _lib.CURVES[self.name]
@@ -137,7 +148,7 @@ class Edwards:
         self._chk(P)
         up = self.name.upper()
         fname = self._field or (curves.CURVES[up] if up in curves.CURVES else curves.W_CURVES[up]).field
-        F = Field(fname, device=self.device) if self.wl == 64 else Field(fname, device=self.device, wl=32)
+        F = Field(fname, device=self.device) if self.wl == 64 else Field(fname, device=self.device, wl=32, plugin_dir=self._plugin_dir)
         return F.modlimbs(P[0]) & F.modlimbs(P[1]) & F.modlimbs(P[2])
 
     def dbl(self, P): return self._un("dbl", P)

@@ -554,11 +554,22 @@ def w32_curve_header_text(name: str) -> str:
     c0 = curves.CURVES[name] if edw else curves.W_CURVES[name]
     c = dataclasses.replace(c0, fp=derive(c0.field, wl=32))
     assert not c.small_x, "a generator given by a small x needs the field's square root at gen()"
+    return w32_curve_header_text_of(c)
+
+
+def w32_curve_header_text_of(c, include: str = None) -> str:
+    """the same for any EdwardsCurve / WeierstrassCurve object whose c.fp is a field of word length 32: the three built-in curves, or a
+    curve generated at that word length (modarith_amd.generate.generate_curve(..., wl=32): w32_curve_<CURVE>.h in the plug-in
+    directory, over `include`, the params_<TAG>_w32.h of a generated field).  A generator given by a small x is emitted as SMALL_X;
+    gen() of edwards.h / weierstrass.h then recovers y with the field's square root, as ecnXXXgen does."""
+    from . import curves
+    edw = isinstance(c, curves.EdwardsCurve)
+    assert c.fp.wl == 32
     L = ["// GENERATED by modarith_amd/emit.py from modarith_amd/curves.py -- do not edit.",
          ("// Edwards curve %s: %d*x^2 + y^2 = 1 + d*x^2*y^2" % (c.name, c.a) if edw else "// Weierstrass curve %s: y^2 = x^3 %+d*x + b" % (c.name, c.a))
          + " over the %s field at word length 32 (%d x %d-bit limbs%s)" % (c.field, c.fp.nlimbs, c.fp.radix, ", Montgomery form" if c.fp.montgomery else ""),
          "#pragma once",
-         '#include "w32_%s.h"' % c.field,
+         '#include "%s"' % (include or "w32_%s.h" % c.field),
          "namespace ma32 {",
          "struct C_%s_W32 {" % c.name,
          "    using FieldParams = P_%s_W32;" % c.field]
@@ -566,18 +577,48 @@ def w32_curve_header_text(name: str) -> str:
         L += ["    static constexpr int A = %d, COF = %d;" % (c.a, c.cof),
               "    static constexpr bool B_SMALL = %s;" % ("true" if c.small_b else "false"),
               "    static constexpr int B_INT = %d;       // CONSTANT_B when small (curve.py:256-257)" % (c.d if c.small_b else 0),
-              "    static constexpr int SMALL_X = 0;     // CONSTANT_X when the generator is given by a small x (curve.py:239-240), else 0",
+              "    static constexpr int SMALL_X = %d;     // CONSTANT_X when the generator is given by a small x (curve.py:239-240), else 0" % (c.gx if c.small_x else 0),
               _switch("b", "unsigned long long", c.internal(c.d) if not c.small_b else [0] * c.fp.nlimbs, _hexu)]
     else:
         L += ["    static constexpr int A = %d, COF = 0;" % c.a,
               "    static constexpr int SMALL_B = %d;   // curve.py's CONSTANT_B when |b| < 2^28, else 0 (b, b3 below are used)" % (c.b if c.small_b else 0),
-              "    static constexpr int SMALL_X = 0;   // curve.py's CONSTANT_X when the generator is given by a small x, else 0",
+              "    static constexpr int SMALL_X = %d;   // curve.py's CONSTANT_X when the generator is given by a small x, else 0" % (c.gx if c.small_x else 0),
               _switch("b", "unsigned long long", c.internal(c.b), _hexu),
               _switch("b3", "unsigned long long", c.internal(3 * c.b), _hexu)]
     L += [_switch("gx", "unsigned long long", c.internal(c.gx), _hexu),
           _switch("gy", "unsigned long long", c.internal(c.gy), _hexu),
           "};", "}  // namespace ma32"]
     return "\n".join(L) + "\n"
+
+
+def w32_curve_mul_wps(nlimbs: int, montgomery: bool, kind: str = "edwards") -> int:
+    """MA_MUL_WPS of a curve unit at word length 32: resident waves per SIMD the scalar-multiplication kernels are register-budgeted for
+    (csrc/curve.h), from cross-compiling for gfx950 (docs/curve_layer.md "Word length 32, any curve"; tools/w32_curve_gen_resources.json).  The three built-in
+    units use 4 at 9-limb pseudo-Mersenne Edwards (ED25519), 3 at 9-limb Montgomery (NIST256) and 2 at 16 limbs (ED448).  A Weierstrass
+    curve over a 9-limb pseudo-Mersenne field (NUMS256W) spills 34 registers under the 128 of four waves and takes 3; 14 limbs fit
+    two waves (253 VGPRs, no scratch).  At 18 limbs the Edwards kernel fits two waves (207 VGPRs); the Weierstrass kernel (NIST521)
+    spills 55 registers there -- in the table-building prologue only -- or runs as one wave on the whole register file without
+    scratch: W32_MUL_WPS_18_WEIERSTRASS holds the measured choice."""
+    if nlimbs <= 9:
+        return 4 if (kind == "edwards" and not montgomery) else 3
+    if nlimbs <= 16 or kind == "edwards":
+        return 2
+    return W32_MUL_WPS_18_WEIERSTRASS
+
+
+# measured (profiles/w32_curve_gen_rate.json, NIST521, 2^19 points): two waves with the prologue-only spill 6.88e6 mul/s and 4.25e6 mul2/s, one wave
+# on the whole register file without scratch 6.10e6 and 3.51e6
+W32_MUL_WPS_18_WEIERSTRASS = 2
+
+
+def w32_curve_unit_text(name: str, kind: str, field: str, nlimbs: int, montgomery: bool, mul_wps: int = None) -> str:
+    """capi_curve_<CURVE>_w32.hip of a generated curve: the lines of csrc/capi_ED25519_w32_ecn.hip over the generated struct"""
+    up, low = name.upper(), name.lower()
+    cls = "ma32::%s<ma32::C_%s_W32>" % ("Edwards" if kind == "edwards" else "Weierstrass", up)
+    return ("// GENERATED by modarith_amd/generate.py -- do not edit.  C-ABI of the curve layer at word length 32 for %s (%s over %s, %d limbs); body: csrc/capi_curve.inc\n"
+            '#include "modarith_amd_w32_curve.h"\nextern "C" {\nMODARITH_AMD_DECLARE_W32_CURVE(%s, %d)\n}\n'
+            "#define MA_MUL_WPS %d\n#include \"w32_curve_%s.h\"\n#include \"%s\"\n#define MA_CURVE_CLASS %s\n#define MA_CNAME %s_w32\n#include \"capi_curve.inc\"\n"
+            % (up, kind, field, nlimbs, low, nlimbs, mul_wps or w32_curve_mul_wps(nlimbs, montgomery, kind), up, "edwards.h" if kind == "edwards" else "weierstrass.h", cls, low))
 
 
 COMB_CURVES = {"NIST256": (286, 5), "SECP256K1": (0, 5)}      # curve -> (log2 of the Montgomery factor of the fused kernels' field form, window width)

@@ -79,7 +79,8 @@ class Field:
 
     DEFAULT_TILE = 4096            # = modarith_amd_recommended_ld(n) for n >= 2 * 4096 (include/modarith_amd.h "TILED")
 
-    def __init__(self, prime: str, device: Optional[torch.device] = None, tile: Optional[int] = DEFAULT_TILE, wl: int = 64):
+    def __init__(self, prime: str, device: Optional[torch.device] = None, tile: Optional[int] = DEFAULT_TILE, wl: int = 64,
+                 plugin_dir: Optional[str] = None):
         self.lib = _lib.load()
         self.flib = self.lib                   # the library that holds this prime's entry points
         if wl not in (64, 32):
@@ -91,18 +92,21 @@ class Field:
             self.params: FieldParams = derive(prime, wl=32)
         elif wl == 32:
             # a field made by generate_w32 (modarith_amd.generate): its kernels live in a plug-in of their own, libmodarith_amd_<TAG>_w32.so
+            # (plugin_dir: where it was generated, if not the default directory)
             from . import generate as _gen
-            if not os.path.exists(_gen.plugin_path(prime, wl=32)) and (prime[:1].isdigit() or "=" in prime):
+            if plugin_dir is not None and not os.path.exists(_gen.plugin_path(prime, plugin_dir, wl=32)):
+                plugin_dir = None              # (not there: the default directory, as generate_curve looks for a curve's field)
+            if not os.path.exists(_gen.plugin_path(prime, plugin_dir, wl=32)) and (prime[:1].isdigit() or "=" in prime):
                 try:
                     prime = _gen.resolve(prime, wl=32).name
                 except _gen.GenerateError:
                     pass
-            if not os.path.exists(_gen.plugin_path(prime, wl=32)):
+            if not os.path.exists(_gen.plugin_path(prime, plugin_dir, wl=32)):
                 raise ValueError("the 32-bit word form is built for %s and generated for %s (got %r): generate it with Field.generate(..., wl=32) "
                                  "or `python -m modarith_amd.generate w32 <prime>`"
-                                 % (", ".join(_lib.W32_PRIMES), ", ".join(m["tag"] for m in _gen.installed(wl=32)) or "no other field yet", prime))
-            self.flib = _lib.load_plugin(prime, wl=32)
-            self.params = _gen.params_of_plugin(prime, wl=32)
+                                 % (", ".join(_lib.W32_PRIMES), ", ".join(m["tag"] for m in _gen.installed(plugin_dir, wl=32)) or "no other field yet", prime))
+            self.flib = _lib.load_plugin(prime, _gen.plugin_path(prime, plugin_dir, wl=32), wl=32)
+            self.params = _gen.params_of_plugin(prime, plugin_dir, wl=32)
         elif prime in _lib.PRIMES:
             self.params: FieldParams = derive(prime)
         else:

@@ -5,6 +5,7 @@
   python -m modarith_amd.generate 64 2**251-9 --time        # ... and run the time.c protocol on the GPU, as the generators do last
   python -m modarith_amd.generate curve NIST224 weierstrass NIST224 -3 0xb405...ffb4 0xffff...2a3d 0xb70e...1d21 0xbd37...7e34
   python -m modarith_amd.generate w32 BP256=0xa9fb57db...5377      # the same field on uint32_t limbs (`monty.py 32 ...`): generate_w32()
+  python -m modarith_amd.generate curve32 NIST384                  # a curve of the table on uint32_t points (`curve.py 32 NIST384`): generate_curve(wl=32)
   python -m modarith_amd.generate --list
 
 This is the counterpart of `python pseudo.py 64 <prime>` / `python monty.py 64 <prime>` (pseudo.py:1461-1473,
@@ -199,12 +200,14 @@ def generate(prime: str, wl: int = 64, family: Optional[str] = None, name: Optio
 
 
 def generate_w32(prime: str, family: Optional[str] = None, name: Optional[str] = None, radix: Optional[int] = None,
-                 plugin_dir: Optional[str] = None, force: bool = False, verbose: bool = False) -> Generated:
+                 plugin_dir: Optional[str] = None, force: bool = False, verbose: bool = False, emit_only: bool = False) -> Generated:
     """generate() at word length 32: `python pseudo.py 32 <prime>` / `python monty.py 32 <prime>`.  Emits, next to each other in the
     plug-in directory, params_<TAG>_w32.h (emit.header_text: struct ma32::P_<TAG>_W32, with the driver's verdict on the shared
     inversion), capi_<TAG>_w32.hip (three lines over csrc/capi_w32.inc and the launch width the limb count allows), field_<TAG>_w32.h
     (the paste-marker shim), libmodarith_amd_<TAG>_w32.so and the metadata <TAG>_w32.json ("wl": 32).  Caching, atomic renames and
-    linking as generate(); the 64-bit plug-in of the same tag is neither needed nor touched.  X25519, NIST256 and X448 are built in."""
+    linking as generate(); the 64-bit plug-in of the same tag is neither needed nor touched.  X25519, NIST256 and X448 are built in.
+    emit_only: write the texts (and, where there is none, the metadata without a hash, so that a curve can be emitted over the tag) and
+    return without calling the compiler."""
     fp = resolve(prime, family, name, radix, wl=32)
     tag = fp.name
     from . import _lib
@@ -226,6 +229,15 @@ def generate_w32(prime: str, family: Optional[str] = None, name: Optional[str] =
     emit._write(hdr, hdr_text)
     emit._write(os.path.join(d, "field_%s.h" % stem), emit.field_shim_text(fp))
     emit._write(unit, unit_text)
+    tmp = ".%d.tmp" % os.getpid()
+    record = {"tag": tag, "wl": 32, "prime": prime, "p": hex(fp.p), "family": fp.family, "radix": fp.radix, "nlimbs": fp.nlimbs,
+              "ept_max": emit.w32_ept_max(fp.nlimbs)}
+    if emit_only:
+        if not os.path.exists(meta):
+            with open(meta + tmp, "w") as f:
+                json.dump(record, f, indent=1)
+            os.replace(meta + tmp, meta)
+        return Generated(tag, lib, fp, False)
     if not force and os.path.exists(lib) and os.path.exists(meta):
         try:
             if json.load(open(meta)).get("hash") == key:
@@ -239,13 +251,11 @@ def generate_w32(prime: str, family: Optional[str] = None, name: Optional[str] =
         raise GenerateError("%s is missing: build it first (python -m modarith_amd.build); plug-ins link against it" % main)
     if verbose:
         print("[modarith_amd] hipcc %s -> %s" % (os.path.basename(unit), os.path.basename(lib)), flush=True)
-    tmp = ".%d.tmp" % os.getpid()
     subprocess.run([HIPCC] + _flags() + ["-c", unit, "-o", obj + tmp], check=True, timeout=int(os.environ.get("MA_BUILD_TIMEOUT", "1500")))
     subprocess.check_call([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib + tmp, obj + tmp, "-L", HERE, "-l:libmodarith_amd.so",
                            "-Wl,-rpath,$ORIGIN/" + os.path.relpath(HERE, d), "-Wl,-rpath," + HERE])
     with open(meta + tmp, "w") as f:
-        json.dump({"tag": tag, "wl": 32, "prime": prime, "p": hex(fp.p), "family": fp.family, "radix": fp.radix, "nlimbs": fp.nlimbs,
-                   "ept_max": emit.w32_ept_max(fp.nlimbs), "hash": key}, f, indent=1)
+        json.dump(dict(record, hash=key), f, indent=1)
     os.replace(obj + tmp, obj)
     os.replace(lib + tmp, lib)
     os.replace(meta + tmp, meta)
@@ -265,17 +275,25 @@ class GeneratedCurve:
     built: bool
 
 
-def curve_plugin_path(name: str, plugin_dir: Optional[str] = None) -> str:
-    return os.path.join(plugin_dir or PLUGIN_DIR, "libmodarith_amd_curve_%s.so" % name.lower())
+def curve_plugin_path(name: str, plugin_dir: Optional[str] = None, wl: int = 64) -> str:
+    return os.path.join(plugin_dir or PLUGIN_DIR, "libmodarith_amd_curve_%s%s.so" % (name.lower(), "" if wl == 64 else "_w32"))
 
 
 def generate_curve(name: str, kind: str, field: str, a: int, b: int, order: int, gx: int, gy: int, cof: int = 0,
-                   plugin_dir: Optional[str] = None, force: bool = False, verbose: bool = False) -> GeneratedCurve:
+                   plugin_dir: Optional[str] = None, force: bool = False, verbose: bool = False, wl: int = 64, emit_only: bool = False,
+                   mul_wps: Optional[int] = None) -> GeneratedCurve:
     """The curve layer (curve.h: ecn_<name>_mul / mul2 / add / dbl / set / get ..., scalar and batched) for a curve that is not in
     curve.py's table.  kind "edwards": a x^2 + y^2 = 1 + b x^2 y^2 with a = +-1 (edwards.c; cof = log2 of the cofactor);
     kind "weierstrass": y^2 = x^3 + a x + b with a = -3 or 0 and prime order (weierstrass.c).  `field`: a built-in prime name or the
     tag of a generated field (generate() first).  One hipcc unit (the scalar-multiplication kernels take about a minute to
-    compile); the plug-in exports what MODARITH_AMD_DECLARE_EDWARDS(<lower-case name>, Nlimbs) declares."""
+    compile); the plug-in exports what MODARITH_AMD_DECLARE_EDWARDS(<lower-case name>, Nlimbs) declares.
+    wl=32: the same curve on uint32_t points (`curve.py 32 <CURVE>`), see _generate_curve_w32; emit_only and mul_wps belong to it."""
+    if wl == 32:
+        return _generate_curve_w32(name, kind, field, a, b, order, gx, gy, cof, plugin_dir, force, verbose, emit_only, mul_wps)
+    if wl != 64:
+        raise GenerateError("word length must be 64 or 32")
+    if emit_only or mul_wps is not None:
+        raise GenerateError("emit_only and mul_wps belong to the 32-bit word form (wl=32)")
     from . import _lib, curves
     from .params import derive
     if kind not in ("edwards", "weierstrass"):
@@ -346,6 +364,143 @@ def generate_curve(name: str, kind: str, field: str, a: int, b: int, order: int,
     os.replace(meta + tmp, meta)
     out.built = True
     return out
+
+
+def _w32_curve_field(field: str, d: str):
+    """the field of a 32-bit curve -> (FieldParams, header to include, generate_w32 argument or None): a built-in 32-bit prime, the
+    tag of a generate_w32 plug-in (next to the curve or in the default directory), or a named prime, which is then generated"""
+    from . import _lib
+    from .params import derive
+    if field in _lib.W32_PRIMES:
+        return derive(field, wl=32), "w32_%s.h" % field, None
+    for where in (d, PLUGIN_DIR):
+        if os.path.exists(os.path.join(where, "%s_w32.json" % field)):
+            meta = json.load(open(os.path.join(where, "%s_w32.json" % field)))
+            fp = params_of_plugin(field, where, wl=32)
+            fp.name = field
+            # (the prime as it was given: a second process generating the same curve reaches the same up-to-date field plug-in)
+            return fp, "params_%s_w32.h" % field, (meta.get("prime", field), meta["family"], meta["radix"], where)
+    if field in NAMED:
+        fp = resolve(field, wl=32)
+        return fp, "params_%s_w32.h" % field, (field, None, None, d)
+    raise GenerateError("field %r is neither built in at word length 32 (%s), nor generated there, nor a named prime: run generate_w32() for it first"
+                        % (field, ", ".join(_lib.W32_PRIMES)))
+
+
+def _generate_curve_w32(name, kind, field, a, b, order, gx, gy, cof, plugin_dir, force, verbose, emit_only, mul_wps) -> GeneratedCurve:
+    """generate_curve() at word length 32: `python curve.py 32 <CURVE>`.  The field is a built-in 32-bit prime, the tag of a generate_w32
+    plug-in, or a named prime (generated first, in the same call).  Emits, next to each other in the plug-in directory,
+    w32_curve_<CURVE>.h (emit.w32_curve_header_text_of: struct ma32::C_<CURVE>_W32), capi_curve_<CURVE>_w32.hip (the lines of
+    csrc/capi_ED25519_w32_ecn.hip, MA_MUL_WPS chosen by emit.w32_curve_mul_wps), libmodarith_amd_curve_<c>_w32.so and
+    curve_<CURVE>_w32.json ("wl": 32).  The unit is compiled as its three MA_CURVE_PART objects, concurrently (the two
+    scalar-multiplication kernels take about half a minute each), and linked into one library that exports what
+    MODARITH_AMD_DECLARE_W32_CURVE(<c>, Nlimbs) declares; `Curve("<CURVE>", wl=32)` loads it.  A name is refused only where it is built in
+    at THIS word length (ED25519, NIST256, ED448).  emit_only: write the texts and return without calling the compiler."""
+    import concurrent.futures as cf
+    from . import curves
+    if kind not in ("edwards", "weierstrass"):
+        raise GenerateError("kind must be 'edwards' or 'weierstrass'")
+    if not _TAG_RE.match(name) or not name[0].isalpha() or name.lower().endswith("_w32"):
+        raise GenerateError("%r cannot name a curve (a C identifier that does not end in _w32, the suffix of this word length's files)" % (name,))
+    up, low = name.upper(), name.lower()
+    if up in emit.W32_CURVES:
+        raise GenerateError("%s is a built-in curve at word length 32" % up)
+    d = plugin_dir or PLUGIN_DIR
+    fp, field_inc, field_gen = _w32_curve_field(field, d)
+    if fp.nlimbs > emit.MAX_GENERATED_LIMBS_W32:
+        raise GenerateError("%d limbs: the 32-bit kernels are built for at most %d limbs" % (fp.nlimbs, emit.MAX_GENERATED_LIMBS_W32))
+    p = fp.p
+    # the checks curve.py leaves to its user, as at 64 bits
+    if kind == "edwards":
+        if a not in (1, -1):
+            raise GenerateError("edwards.c handles a = 1 and a = -1")
+        if gy and (a * gx * gx + gy * gy - 1 - b * gx * gx * gy * gy) % p:
+            raise GenerateError("the generator is not on the curve")
+        c = curves.EdwardsCurve(up, field, a, b, cof, order, gx, gy, fp)
+    else:
+        if a not in (-3, 0):
+            raise GenerateError("weierstrass.c handles a = -3 and a = 0")
+        if gy and (gy * gy - gx ** 3 - a * gx - b) % p:
+            raise GenerateError("the generator is not on the curve")
+        c = curves.WeierstrassCurve(up, field, a, b, order, gx, gy, fp)
+    wps = mul_wps or emit.w32_curve_mul_wps(fp.nlimbs, fp.montgomery, kind)
+    if wps not in (1, 2, 3, 4):
+        raise GenerateError("MA_MUL_WPS is 1 to 4 resident waves per SIMD")
+    hdr_text = emit.w32_curve_header_text_of(c, include=field_inc)
+    unit_text = emit.w32_curve_unit_text(up, kind, field, fp.nlimbs, fp.montgomery, wps)
+    field_text = emit.header_text(fp, generated=field_gen is not None)
+    os.makedirs(d, exist_ok=True)
+    stem = "%s_w32" % up
+    hdr, unit = os.path.join(d, "w32_curve_%s.h" % up), os.path.join(d, "capi_curve_%s.hip" % stem)
+    lib, meta = curve_plugin_path(up, d, 32), os.path.join(d, "curve_%s.json" % stem)
+    from .build import ARCH, FLAGS, HIPCC, _stamp
+    key = hashlib.sha256((" ".join(FLAGS) + "\n" + hdr_text + "\n" + unit_text + "\n" + field_text + "\n" + _stamp()).encode()).hexdigest()
+    out = GeneratedCurve(up, kind, field, lib, fp.nlimbs, fp.nbytes, False)
+    emit._write(hdr, hdr_text)
+    emit._write(unit, unit_text)
+    if field_gen is not None and field_gen[3] == d:
+        emit._write(os.path.join(d, "params_%s_w32.h" % field), field_text)      # (what generate_w32 writes: the curve parts compile beside it)
+    if emit_only:
+        return out
+    field_job = None
+    if field_gen is not None:
+        fg = lambda: generate_w32(field_gen[0], family=field_gen[1], name=field, radix=field_gen[2], plugin_dir=field_gen[3], verbose=verbose)
+        field_job = fg if not os.path.exists(plugin_path(field, field_gen[3], 32)) else None
+    if not force and os.path.exists(lib) and os.path.exists(meta) and field_job is None:
+        try:
+            if json.load(open(meta)).get("hash") == key:
+                return out
+        except (ValueError, OSError):
+            pass
+    if not os.path.exists(HIPCC):
+        raise GenerateError("%s not found: generating a curve needs the ROCm compiler (there is no CPU path)" % HIPCC)
+    if not os.path.exists(os.path.join(HERE, "libmodarith_amd.so")):
+        raise GenerateError("%s is missing: build it first (python -m modarith_amd.build); plug-ins link against it" % os.path.join(HERE, "libmodarith_amd.so"))
+    if verbose:
+        print("[modarith_amd] hipcc %s (three parts) -> %s" % (os.path.basename(unit), os.path.basename(lib)), flush=True)
+    tmp = ".%d.tmp" % os.getpid()
+    inc_dirs = ["-I", os.path.join(HERE, "csrc", "generated"), "-I", os.path.join(HERE, "csrc"), "-I", os.path.join(os.path.dirname(HERE), "include"), "-I", d, "-I", PLUGIN_DIR]
+    parts = [(part, os.path.join(d, "capi_curve_%s_ecn_%s.o" % (stem, nm))) for part, nm in ((1, "mul"), (2, "mul2"), (3, "rest"))]
+    timeout = int(os.environ.get("MA_BUILD_TIMEOUT", "1500"))
+
+    def compile_part(t):
+        subprocess.run([HIPCC] + list(FLAGS) + inc_dirs + ["-DMA_CURVE_PART=%d" % t[0], "-c", unit, "-o", t[1] + tmp], check=True, timeout=timeout)
+
+    with cf.ThreadPoolExecutor(max_workers=4) as ex:
+        jobs = [ex.submit(compile_part, t) for t in parts] + ([ex.submit(field_job)] if field_job else [])
+        for j in jobs:
+            j.result()
+    subprocess.check_call([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib + tmp] + [o + tmp for _, o in parts]
+                          + ["-L", HERE, "-l:libmodarith_amd.so", "-Wl,-rpath,$ORIGIN/" + os.path.relpath(HERE, d), "-Wl,-rpath," + HERE])
+    with open(meta + tmp, "w") as f:
+        json.dump({"curve": up, "wl": 32, "kind": kind, "field": field, "a": a, "b": hex(b) if b >= 0 else "-" + hex(-b), "order": hex(order), "cof": cof,
+                   "gx": hex(gx), "gy": hex(gy), "nlimbs": fp.nlimbs, "radix": fp.radix, "family": fp.family, "nbytes": fp.nbytes, "mul_wps": wps,
+                   "hash": key}, f, indent=1)
+    for _, o in parts:
+        os.replace(o + tmp, o)
+    os.replace(lib + tmp, lib)
+    os.replace(meta + tmp, meta)
+    out.built = True
+    return out
+
+
+def named_curve(name: str) -> dict:
+    """the constants of a curve of curve.py's table (modarith_amd.curves) as generate_curve's arguments"""
+    from . import curves
+    up = name.upper()
+    if up in curves.CURVES:
+        c = curves.CURVES[up]
+        return dict(name=up, kind="edwards", field=c.field, a=c.a, b=c.d, order=c.order, gx=c.gx, gy=c.gy, cof=c.cof)
+    if up in curves.W_CURVES:
+        c = curves.W_CURVES[up]
+        return dict(name=up, kind="weierstrass", field=c.field, a=c.a, b=c.b, order=c.order, gx=c.gx, gy=c.gy)
+    raise GenerateError("%s is not in the curve table (%s)" % (up, ", ".join(list(curves.CURVES) + list(curves.W_CURVES))))
+
+
+def generate_named_curve(name: str, wl: int = 32, **kw) -> GeneratedCurve:
+    """generate_curve() for a curve of curve.py's table: generate_named_curve("NIST384", wl=32) is `python curve.py 32 NIST384`.  (At word
+    length 64 all eleven are built in, and at 32 ED25519, NIST256 and ED448 are: those are refused as generate_curve refuses them.)"""
+    return generate_curve(wl=wl, **named_curve(name), **kw)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -443,16 +598,19 @@ def generate_ladder(name: str, field: str, a24: int, cof: int, twist_secure: boo
 EXAMPLE_LADDERS = (dict(name="M383", field="PM383", a24=516287, cof=3), dict(name="T2519", field="2519", a24=12345, cof=3))
 
 
-def installed_curves(plugin_dir: Optional[str] = None) -> List[dict]:
+def installed_curves(plugin_dir: Optional[str] = None, wl: int = 64) -> List[dict]:
+    """metadata of every curve plug-in of word length wl whose shared object is present (curve_<CURVE>.json; 32: curve_<CURVE>_w32.json)"""
     d = plugin_dir or PLUGIN_DIR
     out = []
     if os.path.isdir(d):
         for f in sorted(os.listdir(d)):
             if f.startswith("curve_") and f.endswith(".json") and os.path.exists(curve_plugin_path(f[6:-5], d)):
                 try:
-                    out.append(json.load(open(os.path.join(d, f))))
+                    m = json.load(open(os.path.join(d, f)))
                 except ValueError:
-                    pass
+                    continue
+                if m.get("wl", 64) == wl:
+                    out.append(m)
     return out
 
 
@@ -583,6 +741,8 @@ def main(argv: List[str]) -> int:
             print("%-12s %-6s %2d x %2d bits  %s   (32-bit words)" % (m["tag"], m["family"], m["nlimbs"], m["radix"], m["prime"]))
         for m in installed_curves():
             print("%-12s %-11s over %-8s a = %d, b = %s" % (m["curve"], m["kind"], m["field"], m["a"], m["b"]))
+        for m in installed_curves(wl=32):
+            print("%-12s %-11s over %-8s a = %d, b = %s   (32-bit words, %d limbs)" % (m["curve"], m["kind"], m["field"], m["a"], m["b"], m["nlimbs"]))
         d = PLUGIN_DIR
         for f in sorted(os.listdir(d)) if os.path.isdir(d) else []:
             if f.startswith("ladder_") and f.endswith(".json") and os.path.exists(ladder_plugin_path(f[7:-5])):
@@ -600,6 +760,18 @@ def main(argv: List[str]) -> int:
             print(e)
             return 2
         print("%s: void rfc7748_%s(const char *bk, const char *bu, char *bv); int rfc7748_%s_batch(bk, bu, bv, n, stream); rfc7748(%r, ...)" % (lib, args[1], args[1], args[1]))
+        return 0
+    if args and args[0] == "curve32":
+        # python -m modarith_amd.generate curve32 <NAME>: a curve of curve.py's table on uint32_t points, the reference's `curve.py 32 <NAME>`
+        if len(args) != 2:
+            print("Valid syntax - python -m modarith_amd.generate curve32 <curve of the table> [--force]")
+            return 2
+        try:
+            g = generate_named_curve(args[1], wl=32, force="--force" in argv, verbose=True)
+        except (GenerateError, ValueError) as e:
+            print(e)
+            return 2
+        print("%s %s: C-ABI ecn_%s_w32_* (MODARITH_AMD_DECLARE_W32_CURVE(%s, %d)); Curve(%r, wl=32)" % ("built" if g.built else "up to date:", g.lib, g.name.lower(), g.name.lower(), g.nlimbs, g.name))
         return 0
     if args and args[0] == "curve":
         # python -m modarith_amd.generate curve <NAME> edwards|weierstrass <field> <a> <b> <order> <gx> <gy> [cof]   (integers: any python literal)
