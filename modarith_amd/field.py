@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .params import FieldParams, derive
+from .params import FieldParams
 
 
 def _stream(device=None) -> int:
@@ -88,41 +88,28 @@ class Field:
         self.wl = wl
         # the container of a limb (the limbs are unsigned), its numpy view, and what the entry points of this word length are called
         self.dtype, self._np, self._sfx = (torch.int64, np.uint64, "") if wl == 64 else (torch.int32, np.uint32, "_w32")
-        if wl == 32 and prime in _lib.W32_PRIMES:
-            self.params: FieldParams = derive(prime, wl=32)
-        elif wl == 32:
-            # a field made by generate_w32 (modarith_amd.generate): its kernels live in a plug-in of their own, libmodarith_amd_<TAG>_w32.so
-            # (plugin_dir: where it was generated, if not the default directory)
-            from . import generate as _gen
-            if plugin_dir is not None and not os.path.exists(_gen.plugin_path(prime, plugin_dir, wl=32)):
-                plugin_dir = None              # (not there: the default directory, as generate_curve looks for a curve's field)
-            if not os.path.exists(_gen.plugin_path(prime, plugin_dir, wl=32)) and (prime[:1].isdigit() or "=" in prime):
-                try:
-                    prime = _gen.resolve(prime, wl=32).name
-                except _gen.GenerateError:
-                    pass
-            if not os.path.exists(_gen.plugin_path(prime, plugin_dir, wl=32)):
-                raise ValueError("the 32-bit word form is built for %s and generated for %s (got %r): generate it with Field.generate(..., wl=32) "
-                                 "or `python -m modarith_amd.generate w32 <prime>`"
-                                 % (", ".join(_lib.W32_PRIMES), ", ".join(m["tag"] for m in _gen.installed(plugin_dir, wl=32)) or "no other field yet", prime))
-            self.flib = _lib.load_plugin(prime, _gen.plugin_path(prime, plugin_dir, wl=32), wl=32)
-            self.params = _gen.params_of_plugin(prime, plugin_dir, wl=32)
-        elif prime in _lib.PRIMES:
-            self.params: FieldParams = derive(prime)
-        else:
-            # a field made by the generator mode (modarith_amd.generate): its kernels live in a plug-in next to the main library
-            from . import generate as _gen
-            if not os.path.exists(_gen.plugin_path(prime)) and (prime[:1].isdigit() or "=" in prime):
-                try:                                   # an expression ("2**251-9", "NAME=0x...") names the field by its tag
-                    prime = _gen.resolve(prime).name
-                except _gen.GenerateError:
-                    pass
-            if not os.path.exists(_gen.plugin_path(prime)):
-                raise ValueError("prime %r is neither built in (%s) nor generated (%s); generate it with Field.generate(...) or "
-                                 "`python -m modarith_amd.generate 64 <prime>`"
-                                 % (prime, ", ".join(_lib.PRIMES), ", ".join(m["tag"] for m in _gen.installed()) or "none"))
-            self.flib = _lib.load_plugin(prime)
-            self.params = _gen.params_of_plugin(prime)
+        # a built-in prime, or a field made by the generator mode (modarith_amd.generate: generate / generate_w32), whose kernels live in
+        # a plug-in of their own; plugin_dir: where it was generated, if not the default directory (looked into after it, as for a curve's field)
+        from . import generate as _gen
+        builtin = _lib.PRIMES if wl == 64 else _lib.W32_PRIMES
+        found = _gen.find_field(prime, plugin_dir, wl, built=True)
+        if found is None and (prime[:1].isdigit() or "=" in prime):
+            try:                                       # an expression ("2**251-9", "NAME=0x...") names the field by its tag
+                prime = _gen.resolve(prime, wl=wl).name
+                found = _gen.find_field(prime, plugin_dir, wl, built=True) if prime not in builtin else None
+            except _gen.GenerateError:
+                pass
+        if found is None and wl == 32:
+            raise ValueError("the 32-bit word form is built for %s and generated for %s (got %r): generate it with Field.generate(..., wl=32) "
+                             "or `python -m modarith_amd.generate w32 <prime>`"
+                             % (", ".join(builtin), ", ".join(m["tag"] for m in _gen.installed(plugin_dir, wl=32)) or "no other field yet", prime))
+        if found is None:
+            raise ValueError("prime %r is neither built in (%s) nor generated (%s); generate it with Field.generate(...) or "
+                             "`python -m modarith_amd.generate 64 <prime>`"
+                             % (prime, ", ".join(builtin), ", ".join(m["tag"] for m in _gen.installed()) or "none"))
+        self.params: FieldParams = found[0]
+        if found[1] is not None:
+            self.flib = _lib.load_plugin(prime, _gen.plugin_path(prime, found[1], wl), wl=wl)
         self.prime = prime
         self.N = self.params.nlimbs
         self.radix = self.params.radix

@@ -41,17 +41,14 @@ Like the generator mode (modarith_amd/generate.py) this needs hipcc where the ch
 from __future__ import annotations
 
 import ctypes
-import hashlib
-import json
 import os
 import re
-import subprocess
 from typing import List, Optional, Sequence
 
 from . import _lib, emit
 from . import generate as _gen
+from .plugin import build_plugin
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 _NAME_RE = re.compile(r"^[A-Za-z][A-Za-z0-9_]*$")
 # op -> (Field<P> function, operand count, takes an int immediate)
 _OPS = {"modmul": 2, "modadd": 2, "modsub": 2, "modsqr": 1, "modneg": 1, "nres": 1, "redc": 1, "modcpy": 1, "modinv": 1, "modmli": 1,
@@ -87,26 +84,13 @@ class Chain:
         if wl not in (64, 32):
             raise ValueError("word length must be 64 or 32 (got %r)" % (wl,))
         self.wl = wl
-        if wl == 32:
-            if prime in _lib.W32_PRIMES:
-                from .params import derive
-                self.params = derive(prime, wl=32)
-                self.builtin = True
-            elif os.path.exists(_gen.plugin_path(prime, wl=32)):
-                self.params = _gen.params_of_plugin(prime, wl=32)      # a field of generate_w32: params_<TAG>_w32.h next to its plug-in
-                self.builtin = False
-            else:
-                raise ValueError("the 32-bit word form is built for %s (got %r) and generated for what `python -m modarith_amd.generate w32 <prime>` "
-                                 "has made; every other field is 64-bit only" % (", ".join(_lib.W32_PRIMES), prime))
-        elif prime in _lib.PRIMES:
-            from .params import derive
-            self.params = derive(prime)
-            self.builtin = True
-        elif os.path.exists(_gen.plugin_path(prime)):
-            self.params = _gen.params_of_plugin(prime)
-            self.builtin = False
-        else:
+        found = _gen.find_field(prime, wl=wl, built=True)
+        if found is None and wl == 32:
+            raise ValueError("the 32-bit word form is built for %s (got %r) and generated for what `python -m modarith_amd.generate w32 <prime>` "
+                             "has made; every other field is 64-bit only" % (", ".join(_lib.W32_PRIMES), prime))
+        if found is None:
             raise ValueError("prime %r is neither built in nor generated (python -m modarith_amd.generate 64 <prime>)" % (prime,))
+        self.params, self.builtin = found[0], found[1] is None      # (generated: params_<TAG>.h / params_<TAG>_w32.h next to its plug-in)
         self.prime, self.name = prime, name
         self.nin = 0
         self.nsel = 0                       # per-element int selectors (modcmv / modcsw): int32 arrays after the element inputs
@@ -542,38 +526,18 @@ class Chain:
 
     def build(self, plugin_dir: Optional[str] = None, force: bool = False, verbose: bool = False, ept: Optional[int] = None, policy: str = "vote", waves: int = 0,
               block: Optional[int] = None) -> "FusedChain":
-        from .build import ARCH, FLAGS, HIPCC, _stamp
+        """one hipcc unit, installed and reused as every plug-in is (modarith_amd/generate.py, modarith_amd/plugin.py)"""
         d = plugin_dir or _gen.PLUGIN_DIR
         os.makedirs(d, exist_ok=True)
         src_text = self.source(ept, policy, waves, block)
         base = "chain_%s_%s" % (self.name, self._tag)
         src, obj, meta = (os.path.join(d, base + e) for e in (".hip", ".o", ".json"))
         lib = self.lib_path(d)
-        key = hashlib.sha256((" ".join(FLAGS) + "\n" + src_text + "\n" + emit.header_text(self.params) + "\n" + _stamp()).encode()).hexdigest()
-        fresh = False
-        if not force and os.path.exists(lib) and os.path.exists(meta):
-            try:
-                fresh = json.load(open(meta)).get("hash") == key
-            except (ValueError, OSError):
-                fresh = False
-        if not fresh:
-            if not os.path.exists(HIPCC):
-                raise RuntimeError("%s not found: fusing a chain needs the ROCm compiler (there is no CPU path)" % HIPCC)
-            emit._write(src, src_text)
-            inc = ["-I", os.path.join(HERE, "csrc", "generated"), "-I", os.path.join(HERE, "csrc"), "-I", os.path.join(os.path.dirname(HERE), "include"), "-I", _gen.PLUGIN_DIR, "-I", d]
-            if verbose:
-                print("[modarith_amd] hipcc %s" % os.path.basename(src), flush=True)
-            tmp = ".%d.tmp" % os.getpid()              # process-private names, moved into place when complete (see generate.py)
-            subprocess.run([HIPCC] + list(FLAGS) + inc + ["-c", src, "-o", obj + tmp], check=True, timeout=int(os.environ.get("MA_BUILD_TIMEOUT", "1500")))
-            subprocess.check_call([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib + tmp, obj + tmp, "-L", HERE, "-l:libmodarith_amd.so",
-                                   "-Wl,-rpath,$ORIGIN/" + os.path.relpath(HERE, d), "-Wl,-rpath," + HERE])
-            with open(meta + tmp, "w") as f:
-                json.dump({"chain": self.name, "prime": self.prime, "wl": self.wl, "inputs": self.nin, "selectors": self.nsel, "outputs": len(self.outs),
-                           "ops": [o[0] for o in self.ops], "symbol": self.symbol, "hash": key}, f, indent=1)
-            os.replace(obj + tmp, obj)
-            os.replace(lib + tmp, lib)
-            os.replace(meta + tmp, meta)
-        return FusedChain(self, lib, built=not fresh)
+        emit._write(src, src_text)
+        record = {"chain": self.name, "prime": self.prime, "wl": self.wl, "inputs": self.nin, "selectors": self.nsel, "outputs": len(self.outs),
+                  "ops": [o[0] for o in self.ops], "symbol": self.symbol}
+        built = build_plugin(d, lib, meta, record, _gen.key_of(src_text, emit.header_text(self.params)), [(src, obj, [])], "chain", force, verbose)
+        return FusedChain(self, lib, built)
 
 
 class FusedChain:

@@ -25,6 +25,14 @@ name (`NAME=<expression>` or `name=`), as monty.py insists ("Modulus must have a
 length 32, a plug-in `libmodarith_amd_<TAG>_w32.so` over csrc/capi_w32.inc that exports what MODARITH_AMD_DECLARE_W32(<TAG>) of
 include/modarith_amd_w32.h declares, next to (and independent of) the 64-bit plug-in of the same tag; `Field("<TAG>", wl=32)` loads it.
 
+How a plug-in is installed and reused -- fields, curves and ladders here, and the fused chains of modarith_amd/fuse.py, all through
+build_plugin() of modarith_amd/plugin.py: the generator writes its emitted texts (only those that differ from what is there) and hashes
+them with the compile flags and every kernel source (key_of).  A plug-in whose metadata records that hash is current and is returned
+with built = False, its directory untouched.  Otherwise the units are compiled and linked against libmodarith_amd.so and the metadata
+is written, all under names private to the call, and then moved into place -- objects, library, metadata last -- so that another
+thread or process generating or loading the same plug-in never sees a half-written file, and a failed compile leaves nothing behind.
+A field is looked for among the built-in primes, then in the directory being generated into, then in the default one (find_field).
+
 There is no CPU path here either: the plug-in contains GPU kernels only, and a missing hipcc is an error.
 """
 from __future__ import annotations
@@ -33,13 +41,13 @@ import hashlib
 import json
 import os
 import re
-import subprocess
 import sys
 from dataclasses import dataclass
 from typing import List, Optional
 
 from . import emit
 from .params import NAMED, RADIX_32, FieldParams, derive_monty, derive_pseudo
+from .plugin import build_plugin, tmp_suffix
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PLUGIN_DIR = os.environ.get("MA_PLUGIN_DIR", os.path.join(HERE, "plugins"))
@@ -127,76 +135,84 @@ def resolve(prime: str, family: Optional[str] = None, name: Optional[str] = None
     return fp
 
 
-def _flags() -> List[str]:
-    from .build import FLAGS
-    return list(FLAGS) + ["-I", os.path.join(HERE, "csrc", "generated"), "-I", os.path.join(HERE, "csrc")]
-
-
-def _key(fp: FieldParams, tag: str) -> str:
-    """what a plug-in was made from: the constants, the flags and every kernel source (path-independent, so a plug-in built in one
+def key_of(*texts: str) -> str:
+    """what a plug-in was made from: the flags, its emitted texts and every kernel source (path-independent, so a plug-in built in one
     checkout is recognised as current in a copy of it)"""
     from .build import FLAGS, _stamp
-    h = hashlib.sha256((" ".join(FLAGS) + "\n" + emit.header_text(fp) + "\n" + emit.capi_unit_text(tag) + "\n" + _stamp()).encode())
-    return h.hexdigest()
+    return hashlib.sha256("\n".join([" ".join(FLAGS)] + list(texts) + [_stamp()]).encode()).hexdigest()
 
 
 def plugin_path(tag: str, plugin_dir: Optional[str] = None, wl: int = 64) -> str:
     return os.path.join(plugin_dir or PLUGIN_DIR, "libmodarith_amd_%s%s.so" % (tag, "" if wl == 64 else "_w32"))
 
 
+def _meta_path(tag: str, plugin_dir: Optional[str] = None, wl: int = 64) -> str:
+    return os.path.join(plugin_dir or PLUGIN_DIR, "%s%s.json" % (tag, "" if wl == 64 else "_w32"))
+
+
+def find_field(field: str, d: Optional[str] = None, wl: int = 64, built: bool = False):
+    """the field a curve, ladder, chain or Field names -> (FieldParams, directory of its plug-in, or None for a built-in prime); None
+    when there is no such field.  Built-in primes first, then the directory d, then the default one.  A generated field is there when
+    its metadata is (generate_w32's emit_only writes no more); built=True asks for its shared object instead."""
+    from . import _lib
+    from .params import derive
+    if field in (_lib.PRIMES if wl == 64 else _lib.W32_PRIMES):
+        return derive(field, wl=wl), None
+    for where in (d or PLUGIN_DIR, PLUGIN_DIR):
+        if os.path.exists((plugin_path if built else _meta_path)(field, where, wl)):
+            return params_of_plugin(field, where, wl), where
+    return None
+
+
+def _generate_field(prime, wl, family, name, radix, plugin_dir, force, verbose, emit_only=False) -> Generated:
+    """generate() and generate_w32(): the word lengths differ in the built-in list, the limb cap, the file stem and the unit text"""
+    from . import _lib
+    w32 = wl == 32
+    builtin, cap = (_lib.W32_PRIMES, emit.MAX_GENERATED_LIMBS_W32) if w32 else (_lib.PRIMES, emit.MAX_GENERATED_LIMBS)
+    fp = resolve(prime, family, name, radix, wl=wl)
+    tag = fp.name
+    if tag in builtin and NAMED.get(tag, (None,))[0] == fp.p and (family is None or NAMED[tag][1] == fp.family) and radix is None:
+        return Generated(tag, _lib.LIB_PATH, fp, False)         # a built-in prime: nothing to generate
+    if tag in builtin:
+        raise GenerateError("%s names a built-in field with other constants; choose another name" % tag)
+    if fp.nlimbs > cap and w32:
+        raise GenerateError("%d limbs of %d bits: the 32-bit kernels keep every operand in registers and are built for at most %d limbs "
+                            "(no streaming kernel beyond that has been shown free of scratch)" % (fp.nlimbs, fp.radix, cap))
+    if fp.nlimbs > cap:
+        raise GenerateError("%d limbs: the kernels keep every operand in registers and are built for at most %d limbs" % (fp.nlimbs, cap))
+    d = plugin_dir or PLUGIN_DIR
+    os.makedirs(d, exist_ok=True)
+    at = lambda f: os.path.join(d, f % (tag + "_w32" if w32 else tag))
+    unit, lib, meta = at("capi_%s.hip"), plugin_path(tag, d, wl), at("%s.json")
+    hdr_text = emit.header_text(fp, generated=w32)
+    unit_text = emit.capi_unit_text_w32(tag, fp.nlimbs) if w32 else emit.capi_unit_text(tag)
+    key = key_of(hdr_text, unit_text)           # (the 64-bit unit as emit gives it: its include is redirected below, for a unit in d)
+    emit._write(at("params_%s.h"), hdr_text)
+    # the paste-marker shim of this field, next to its plug-in: what a consumer includes where the reference says "paste field.c here"
+    emit._write(at("field_%s.h"), emit.field_shim_text(fp, tag))
+    emit._write(unit, unit_text.replace('"../capi_prime.inc"', '"capi_prime.inc"'))
+    record = {"tag": tag, "prime": prime, "p": hex(fp.p), "family": fp.family, "radix": fp.radix, "nlimbs": fp.nlimbs}
+    if w32:
+        record.update(wl=32, ept_max=emit.w32_ept_max(fp.nlimbs))
+    if emit_only:
+        if not os.path.exists(meta):
+            tmp = meta + tmp_suffix()
+            with open(tmp, "w") as f:
+                json.dump(record, f, indent=1)
+            os.replace(tmp, meta)
+        return Generated(tag, lib, fp, False)
+    built = build_plugin(d, lib, meta, record, key, [(unit, at("capi_%s.o"), [])], "field", force, verbose, error=GenerateError)
+    return Generated(tag, lib, fp, built)
+
+
 def generate(prime: str, wl: int = 64, family: Optional[str] = None, name: Optional[str] = None, radix: Optional[int] = None,
              plugin_dir: Optional[str] = None, force: bool = False, verbose: bool = False) -> Generated:
-    """derive the constants of `prime`, emit them, compile the kernels for it; returns the plug-in to load.
-    An existing plug-in is reused when neither the constants nor any kernel source it was compiled from have changed."""
+    """derive the constants of `prime`, emit them (params_<TAG>.h, field_<TAG>.h, capi_<TAG>.hip), compile the kernels for it; returns
+    the plug-in to load."""
     if wl != 64:
         raise GenerateError("generate() builds 64-bit words only (u64 limbs, 128-bit column sums); the 32-bit form is generate_w32() / "
                             "`python -m modarith_amd.generate w32 <prime>` (include/modarith_amd_w32.h), the 16-bit form does not exist")
-    fp = resolve(prime, family, name, radix)
-    tag = fp.name
-    from . import _lib
-    if tag in _lib.PRIMES and NAMED.get(tag, (None,))[0] == fp.p and (family is None or NAMED[tag][1] == fp.family) and radix is None:
-        return Generated(tag, _lib.LIB_PATH, fp, False)         # a built-in prime: nothing to generate
-    if tag in _lib.PRIMES:
-        raise GenerateError("%s names a built-in field with other constants; choose another name" % tag)
-    if fp.nlimbs > emit.MAX_GENERATED_LIMBS:
-        raise GenerateError("%d limbs: the kernels keep every operand in registers and are built for at most %d limbs" % (fp.nlimbs, emit.MAX_GENERATED_LIMBS))
-    d = plugin_dir or PLUGIN_DIR
-    os.makedirs(d, exist_ok=True)
-    hdr, unit = os.path.join(d, "params_%s.h" % tag), os.path.join(d, "capi_%s.hip" % tag)
-    obj, lib, meta = os.path.join(d, "capi_%s.o" % tag), plugin_path(tag, d), os.path.join(d, "%s.json" % tag)
-    key = _key(fp, tag)
-    emit._write(hdr, emit.header_text(fp))
-    # the paste-marker shim of this field, next to its plug-in: what a consumer includes where the reference says "paste field.c here"
-    emit._write(os.path.join(d, "field_%s.h" % tag), emit.field_shim_text(fp, tag))
-    emit._write(unit, emit.capi_unit_text(tag).replace('"../capi_prime.inc"', '"capi_prime.inc"'))
-    from .build import ARCH, HIPCC
-    cmd = [HIPCC] + _flags() + ["-c", unit]
-    if not force and os.path.exists(lib) and os.path.exists(meta):
-        try:
-            if json.load(open(meta)).get("hash") == key:
-                return Generated(tag, lib, fp, False)
-        except (ValueError, OSError):
-            pass
-    if not os.path.exists(HIPCC):
-        raise GenerateError("%s not found: generating a field needs the ROCm compiler (there is no CPU path)" % HIPCC)
-    main = os.path.join(HERE, "libmodarith_amd.so")
-    if not os.path.exists(main):
-        raise GenerateError("%s is missing: build it first (python -m modarith_amd.build); plug-ins link against it" % main)
-    if verbose:
-        print("[modarith_amd] hipcc %s -> %s" % (os.path.basename(unit), os.path.basename(lib)), flush=True)
-    # object, library and metadata are written under process-private names and moved into place: another process (a second rank,
-    # a parallel test worker) generating or loading the same plug-in never sees a half-written file
-    tmp = ".%d.tmp" % os.getpid()
-    subprocess.run(cmd + ["-o", obj + tmp], check=True, timeout=int(os.environ.get("MA_BUILD_TIMEOUT", "1500")))
-    rel = os.path.relpath(HERE, d)
-    subprocess.check_call([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib + tmp, obj + tmp, "-L", HERE, "-l:libmodarith_amd.so",
-                           "-Wl,-rpath,$ORIGIN/" + rel, "-Wl,-rpath," + HERE])
-    with open(meta + tmp, "w") as f:
-        json.dump({"tag": tag, "prime": prime, "p": hex(fp.p), "family": fp.family, "radix": fp.radix, "nlimbs": fp.nlimbs, "hash": key}, f, indent=1)
-    os.replace(obj + tmp, obj)
-    os.replace(lib + tmp, lib)
-    os.replace(meta + tmp, meta)
-    return Generated(tag, lib, fp, True)
+    return _generate_field(prime, 64, family, name, radix, plugin_dir, force, verbose)
 
 
 def generate_w32(prime: str, family: Optional[str] = None, name: Optional[str] = None, radix: Optional[int] = None,
@@ -204,62 +220,11 @@ def generate_w32(prime: str, family: Optional[str] = None, name: Optional[str] =
     """generate() at word length 32: `python pseudo.py 32 <prime>` / `python monty.py 32 <prime>`.  Emits, next to each other in the
     plug-in directory, params_<TAG>_w32.h (emit.header_text: struct ma32::P_<TAG>_W32, with the driver's verdict on the shared
     inversion), capi_<TAG>_w32.hip (three lines over csrc/capi_w32.inc and the launch width the limb count allows), field_<TAG>_w32.h
-    (the paste-marker shim), libmodarith_amd_<TAG>_w32.so and the metadata <TAG>_w32.json ("wl": 32).  Caching, atomic renames and
-    linking as generate(); the 64-bit plug-in of the same tag is neither needed nor touched.  X25519, NIST256 and X448 are built in.
+    (the paste-marker shim), libmodarith_amd_<TAG>_w32.so and the metadata <TAG>_w32.json ("wl": 32).  The 64-bit plug-in of the same
+    tag is neither needed nor touched.  X25519, NIST256 and X448 are built in.
     emit_only: write the texts (and, where there is none, the metadata without a hash, so that a curve can be emitted over the tag) and
     return without calling the compiler."""
-    fp = resolve(prime, family, name, radix, wl=32)
-    tag = fp.name
-    from . import _lib
-    if tag in _lib.W32_PRIMES and NAMED[tag][0] == fp.p and (family is None or NAMED[tag][1] == fp.family) and radix is None:
-        return Generated(tag, _lib.LIB_PATH, fp, False)         # a built-in prime: nothing to generate
-    if tag in _lib.W32_PRIMES:
-        raise GenerateError("%s names a built-in field with other constants; choose another name" % tag)
-    if fp.nlimbs > emit.MAX_GENERATED_LIMBS_W32:
-        raise GenerateError("%d limbs of %d bits: the 32-bit kernels keep every operand in registers and are built for at most %d limbs "
-                            "(no streaming kernel beyond that has been shown free of scratch)" % (fp.nlimbs, fp.radix, emit.MAX_GENERATED_LIMBS_W32))
-    d = plugin_dir or PLUGIN_DIR
-    os.makedirs(d, exist_ok=True)
-    stem = "%s_w32" % tag
-    hdr, unit = os.path.join(d, "params_%s.h" % stem), os.path.join(d, "capi_%s.hip" % stem)
-    obj, lib, meta = os.path.join(d, "capi_%s.o" % stem), plugin_path(tag, d, 32), os.path.join(d, "%s.json" % stem)
-    hdr_text, unit_text = emit.header_text(fp, generated=True), emit.capi_unit_text_w32(tag, fp.nlimbs)
-    from .build import ARCH, FLAGS, HIPCC, _stamp
-    key = hashlib.sha256((" ".join(FLAGS) + "\n" + hdr_text + "\n" + unit_text + "\n" + _stamp()).encode()).hexdigest()
-    emit._write(hdr, hdr_text)
-    emit._write(os.path.join(d, "field_%s.h" % stem), emit.field_shim_text(fp))
-    emit._write(unit, unit_text)
-    tmp = ".%d.tmp" % os.getpid()
-    record = {"tag": tag, "wl": 32, "prime": prime, "p": hex(fp.p), "family": fp.family, "radix": fp.radix, "nlimbs": fp.nlimbs,
-              "ept_max": emit.w32_ept_max(fp.nlimbs)}
-    if emit_only:
-        if not os.path.exists(meta):
-            with open(meta + tmp, "w") as f:
-                json.dump(record, f, indent=1)
-            os.replace(meta + tmp, meta)
-        return Generated(tag, lib, fp, False)
-    if not force and os.path.exists(lib) and os.path.exists(meta):
-        try:
-            if json.load(open(meta)).get("hash") == key:
-                return Generated(tag, lib, fp, False)
-        except (ValueError, OSError):
-            pass
-    if not os.path.exists(HIPCC):
-        raise GenerateError("%s not found: generating a field needs the ROCm compiler (there is no CPU path)" % HIPCC)
-    main = os.path.join(HERE, "libmodarith_amd.so")
-    if not os.path.exists(main):
-        raise GenerateError("%s is missing: build it first (python -m modarith_amd.build); plug-ins link against it" % main)
-    if verbose:
-        print("[modarith_amd] hipcc %s -> %s" % (os.path.basename(unit), os.path.basename(lib)), flush=True)
-    subprocess.run([HIPCC] + _flags() + ["-c", unit, "-o", obj + tmp], check=True, timeout=int(os.environ.get("MA_BUILD_TIMEOUT", "1500")))
-    subprocess.check_call([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib + tmp, obj + tmp, "-L", HERE, "-l:libmodarith_amd.so",
-                           "-Wl,-rpath,$ORIGIN/" + os.path.relpath(HERE, d), "-Wl,-rpath," + HERE])
-    with open(meta + tmp, "w") as f:
-        json.dump(dict(record, hash=key), f, indent=1)
-    os.replace(obj + tmp, obj)
-    os.replace(lib + tmp, lib)
-    os.replace(meta + tmp, meta)
-    return Generated(tag, lib, fp, True)
+    return _generate_field(prime, 32, family, name, radix, plugin_dir, force, verbose, emit_only)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -279,6 +244,30 @@ def curve_plugin_path(name: str, plugin_dir: Optional[str] = None, wl: int = 64)
     return os.path.join(plugin_dir or PLUGIN_DIR, "libmodarith_amd_curve_%s%s.so" % (name.lower(), "" if wl == 64 else "_w32"))
 
 
+def _curve_definition(kind, up, field, a, b, order, gx, gy, cof, fp):
+    """the checks curve.py leaves to its user (the form edwards.c / weierstrass.c handles, the generator on the curve) -> the
+    curves.EdwardsCurve or curves.WeierstrassCurve of the definition, at the word length of fp"""
+    from . import curves
+    if kind == "edwards":
+        if a not in (1, -1):
+            raise GenerateError("edwards.c handles a = 1 and a = -1")
+        on_curve = a * gx * gx + gy * gy - 1 - b * gx * gx * gy * gy
+    else:
+        if a not in (-3, 0):
+            raise GenerateError("weierstrass.c handles a = -3 and a = 0")
+        on_curve = gy * gy - gx ** 3 - a * gx - b
+    if gy and on_curve % fp.p:
+        raise GenerateError("the generator is not on the curve")
+    if kind == "edwards":
+        return curves.EdwardsCurve(up, field, a, b, cof, order, gx, gy, fp)
+    return curves.WeierstrassCurve(up, field, a, b, order, gx, gy, fp)
+
+
+def _curve_record(c, kind, a, b, cof, fp) -> dict:
+    return {"curve": c.name, "kind": kind, "field": c.field, "a": a, "b": hex(b) if b >= 0 else "-" + hex(-b), "order": hex(c.order), "cof": cof,
+            "gx": hex(c.gx), "gy": hex(c.gy), "nlimbs": fp.nlimbs, "nbytes": fp.nbytes}
+
+
 def generate_curve(name: str, kind: str, field: str, a: int, b: int, order: int, gx: int, gy: int, cof: int = 0,
                    plugin_dir: Optional[str] = None, force: bool = False, verbose: bool = False, wl: int = 64, emit_only: bool = False,
                    mul_wps: Optional[int] = None) -> GeneratedCurve:
@@ -288,101 +277,56 @@ def generate_curve(name: str, kind: str, field: str, a: int, b: int, order: int,
     tag of a generated field (generate() first).  One hipcc unit (the scalar-multiplication kernels take about a minute to
     compile); the plug-in exports what MODARITH_AMD_DECLARE_EDWARDS(<lower-case name>, Nlimbs) declares.
     wl=32: the same curve on uint32_t points (`curve.py 32 <CURVE>`), see _generate_curve_w32; emit_only and mul_wps belong to it."""
-    if wl == 32:
-        return _generate_curve_w32(name, kind, field, a, b, order, gx, gy, cof, plugin_dir, force, verbose, emit_only, mul_wps)
-    if wl != 64:
+    if wl not in (64, 32):
         raise GenerateError("word length must be 64 or 32")
-    if emit_only or mul_wps is not None:
+    if wl == 64 and (emit_only or mul_wps is not None):
         raise GenerateError("emit_only and mul_wps belong to the 32-bit word form (wl=32)")
-    from . import _lib, curves
-    from .params import derive
     if kind not in ("edwards", "weierstrass"):
         raise GenerateError("kind must be 'edwards' or 'weierstrass'")
+    if wl == 32:
+        return _generate_curve_w32(name, kind, field, a, b, order, gx, gy, cof, plugin_dir, force, verbose, emit_only, mul_wps)
+    from . import _lib
     if not _TAG_RE.match(name) or not name[0].isalpha():
         raise GenerateError("%r cannot be part of a C identifier" % (name,))
     up, low = name.upper(), name.lower()
     if low in _lib.CURVES:
         raise GenerateError("%s is a built-in curve" % up)
     d = plugin_dir or PLUGIN_DIR
-    if field in _lib.PRIMES:
-        fp = derive(field)
-    elif os.path.exists(os.path.join(d, "%s.json" % field)):
-        fp = params_of_plugin(field, d)
-    elif os.path.exists(os.path.join(PLUGIN_DIR, "%s.json" % field)):
-        fp = params_of_plugin(field)
-    else:
+    found = find_field(field, d)
+    if found is None:
         raise GenerateError("field %r is neither built in nor generated: run generate() for it first" % (field,))
-    p = fp.p
-    # the checks curve.py leaves to its user: the generator is on the curve, the order annihilates it
+    fp = found[0]
+    c = _curve_definition(kind, up, field, a, b, order, gx, gy, cof, fp)
     if kind == "edwards":
-        if a not in (1, -1):
-            raise GenerateError("edwards.c handles a = 1 and a = -1")
-        if gy and (a * gx * gx + gy * gy - 1 - b * gx * gx * gy * gy) % p:
-            raise GenerateError("the generator is not on the curve")
-        c = curves.EdwardsCurve(up, field, a, b, cof, order, gx, gy, fp)
-        hdr_text = emit.curve_header_text_of(c)
-        cls, inc = "ma::Edwards<ma::C_%s>" % up, "edwards.h"
+        hdr_text, cls, inc = emit.curve_header_text_of(c), "ma::Edwards<ma::C_%s>" % up, "edwards.h"
     else:
-        if a not in (-3, 0):
-            raise GenerateError("weierstrass.c handles a = -3 and a = 0")
-        if gy and (gy * gy - gx ** 3 - a * gx - b) % p:
-            raise GenerateError("the generator is not on the curve")
-        c = curves.WeierstrassCurve(up, field, a, b, order, gx, gy, fp)
-        hdr_text = emit.wcurve_header_text_of(c)
-        cls, inc = "ma::Weierstrass<ma::C_%s>" % up, "weierstrass.h"
+        hdr_text, cls, inc = emit.wcurve_header_text_of(c), "ma::Weierstrass<ma::C_%s>" % up, "weierstrass.h"
     unit_text = ("// GENERATED by modarith_amd/generate.py -- do not edit.  C-ABI of the curve layer for %s (%s over %s); body: csrc/capi_curve.inc\n"
                  '#include "modarith_amd.h"\nextern "C" {\nMODARITH_AMD_DECLARE_EDWARDS(%s, %d)\n}\n#include "curve_%s.h"\n#include "%s"\n'
                  "#define MA_CURVE_CLASS %s\n#define MA_CNAME %s\n#include \"capi_curve.inc\"\n" % (up, kind, field, low, fp.nlimbs, up, inc, cls, low))
     os.makedirs(d, exist_ok=True)
-    hdr, unit = os.path.join(d, "curve_%s.h" % up), os.path.join(d, "capi_curve_%s.hip" % up)
-    obj, lib, meta = os.path.join(d, "capi_curve_%s.o" % up), curve_plugin_path(up, d), os.path.join(d, "curve_%s.json" % up)
-    from .build import ARCH, FLAGS, HIPCC, _stamp
-    key = hashlib.sha256((" ".join(FLAGS) + "\n" + hdr_text + "\n" + unit_text + "\n" + emit.header_text(fp) + "\n" + _stamp()).encode()).hexdigest()
-    out = GeneratedCurve(up, kind, field, lib, fp.nlimbs, fp.nbytes, False)
-    if not force and os.path.exists(lib) and os.path.exists(meta):
-        try:
-            if json.load(open(meta)).get("hash") == key:
-                return out
-        except (ValueError, OSError):
-            pass
-    if not os.path.exists(HIPCC):
-        raise GenerateError("%s not found: generating a curve needs the ROCm compiler (there is no CPU path)" % HIPCC)
-    emit._write(hdr, hdr_text)
+    unit, lib, meta = os.path.join(d, "capi_curve_%s.hip" % up), curve_plugin_path(up, d), os.path.join(d, "curve_%s.json" % up)
+    emit._write(os.path.join(d, "curve_%s.h" % up), hdr_text)
     emit._write(unit, unit_text)
-    if verbose:
-        print("[modarith_amd] hipcc %s -> %s" % (os.path.basename(unit), os.path.basename(lib)), flush=True)
-    tmp = ".%d.tmp" % os.getpid()
-    inc_dirs = ["-I", os.path.join(HERE, "csrc", "generated"), "-I", os.path.join(HERE, "csrc"), "-I", os.path.join(os.path.dirname(HERE), "include"), "-I", PLUGIN_DIR, "-I", d]
-    subprocess.run([HIPCC] + list(FLAGS) + inc_dirs + ["-c", unit, "-o", obj + tmp], check=True, timeout=int(os.environ.get("MA_BUILD_TIMEOUT", "1500")))
-    subprocess.check_call([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib + tmp, obj + tmp, "-L", HERE, "-l:libmodarith_amd.so",
-                           "-Wl,-rpath,$ORIGIN/" + os.path.relpath(HERE, d), "-Wl,-rpath," + HERE])
-    with open(meta + tmp, "w") as f:
-        json.dump({"curve": up, "kind": kind, "field": field, "a": a, "b": hex(b) if b >= 0 else "-" + hex(-b), "order": hex(order), "cof": cof,
-                   "gx": hex(gx), "gy": hex(gy), "nlimbs": fp.nlimbs, "nbytes": fp.nbytes, "hash": key}, f, indent=1)
-    os.replace(obj + tmp, obj)
-    os.replace(lib + tmp, lib)
-    os.replace(meta + tmp, meta)
-    out.built = True
-    return out
+    built = build_plugin(d, lib, meta, _curve_record(c, kind, a, b, cof, fp), key_of(hdr_text, unit_text, emit.header_text(fp)),
+                         [(unit, os.path.join(d, "capi_curve_%s.o" % up), [])], "curve", force, verbose, error=GenerateError)
+    return GeneratedCurve(up, kind, field, lib, fp.nlimbs, fp.nbytes, built)
 
 
 def _w32_curve_field(field: str, d: str):
     """the field of a 32-bit curve -> (FieldParams, header to include, generate_w32 argument or None): a built-in 32-bit prime, the
     tag of a generate_w32 plug-in (next to the curve or in the default directory), or a named prime, which is then generated"""
     from . import _lib
-    from .params import derive
-    if field in _lib.W32_PRIMES:
-        return derive(field, wl=32), "w32_%s.h" % field, None
-    for where in (d, PLUGIN_DIR):
-        if os.path.exists(os.path.join(where, "%s_w32.json" % field)):
-            meta = json.load(open(os.path.join(where, "%s_w32.json" % field)))
-            fp = params_of_plugin(field, where, wl=32)
-            fp.name = field
-            # (the prime as it was given: a second process generating the same curve reaches the same up-to-date field plug-in)
-            return fp, "params_%s_w32.h" % field, (meta.get("prime", field), meta["family"], meta["radix"], where)
+    found = find_field(field, d, 32)
+    if found is not None:
+        fp, where = found
+        if where is None:
+            return fp, "w32_%s.h" % field, None
+        meta = json.load(open(_meta_path(field, where, 32)))
+        # (the prime as it was given: a second process generating the same curve reaches the same up-to-date field plug-in)
+        return fp, "params_%s_w32.h" % field, (meta.get("prime", field), meta["family"], meta["radix"], where)
     if field in NAMED:
-        fp = resolve(field, wl=32)
-        return fp, "params_%s_w32.h" % field, (field, None, None, d)
+        return resolve(field, wl=32), "params_%s_w32.h" % field, (field, None, None, d)
     raise GenerateError("field %r is neither built in at word length 32 (%s), nor generated there, nor a named prime: run generate_w32() for it first"
                         % (field, ", ".join(_lib.W32_PRIMES)))
 
@@ -396,33 +340,16 @@ def _generate_curve_w32(name, kind, field, a, b, order, gx, gy, cof, plugin_dir,
     scalar-multiplication kernels take about half a minute each), and linked into one library that exports what
     MODARITH_AMD_DECLARE_W32_CURVE(<c>, Nlimbs) declares; `Curve("<CURVE>", wl=32)` loads it.  A name is refused only where it is built in
     at THIS word length (ED25519, NIST256, ED448).  emit_only: write the texts and return without calling the compiler."""
-    import concurrent.futures as cf
-    from . import curves
-    if kind not in ("edwards", "weierstrass"):
-        raise GenerateError("kind must be 'edwards' or 'weierstrass'")
     if not _TAG_RE.match(name) or not name[0].isalpha() or name.lower().endswith("_w32"):
         raise GenerateError("%r cannot name a curve (a C identifier that does not end in _w32, the suffix of this word length's files)" % (name,))
-    up, low = name.upper(), name.lower()
+    up = name.upper()
     if up in emit.W32_CURVES:
         raise GenerateError("%s is a built-in curve at word length 32" % up)
     d = plugin_dir or PLUGIN_DIR
     fp, field_inc, field_gen = _w32_curve_field(field, d)
     if fp.nlimbs > emit.MAX_GENERATED_LIMBS_W32:
         raise GenerateError("%d limbs: the 32-bit kernels are built for at most %d limbs" % (fp.nlimbs, emit.MAX_GENERATED_LIMBS_W32))
-    p = fp.p
-    # the checks curve.py leaves to its user, as at 64 bits
-    if kind == "edwards":
-        if a not in (1, -1):
-            raise GenerateError("edwards.c handles a = 1 and a = -1")
-        if gy and (a * gx * gx + gy * gy - 1 - b * gx * gx * gy * gy) % p:
-            raise GenerateError("the generator is not on the curve")
-        c = curves.EdwardsCurve(up, field, a, b, cof, order, gx, gy, fp)
-    else:
-        if a not in (-3, 0):
-            raise GenerateError("weierstrass.c handles a = -3 and a = 0")
-        if gy and (gy * gy - gx ** 3 - a * gx - b) % p:
-            raise GenerateError("the generator is not on the curve")
-        c = curves.WeierstrassCurve(up, field, a, b, order, gx, gy, fp)
+    c = _curve_definition(kind, up, field, a, b, order, gx, gy, cof, fp)
     wps = mul_wps or emit.w32_curve_mul_wps(fp.nlimbs, fp.montgomery, kind)
     if wps not in (1, 2, 3, 4):
         raise GenerateError("MA_MUL_WPS is 1 to 4 resident waves per SIMD")
@@ -431,56 +358,21 @@ def _generate_curve_w32(name, kind, field, a, b, order, gx, gy, cof, plugin_dir,
     field_text = emit.header_text(fp, generated=field_gen is not None)
     os.makedirs(d, exist_ok=True)
     stem = "%s_w32" % up
-    hdr, unit = os.path.join(d, "w32_curve_%s.h" % up), os.path.join(d, "capi_curve_%s.hip" % stem)
-    lib, meta = curve_plugin_path(up, d, 32), os.path.join(d, "curve_%s.json" % stem)
-    from .build import ARCH, FLAGS, HIPCC, _stamp
-    key = hashlib.sha256((" ".join(FLAGS) + "\n" + hdr_text + "\n" + unit_text + "\n" + field_text + "\n" + _stamp()).encode()).hexdigest()
+    unit, lib, meta = os.path.join(d, "capi_curve_%s.hip" % stem), curve_plugin_path(up, d, 32), os.path.join(d, "curve_%s.json" % stem)
     out = GeneratedCurve(up, kind, field, lib, fp.nlimbs, fp.nbytes, False)
-    emit._write(hdr, hdr_text)
+    emit._write(os.path.join(d, "w32_curve_%s.h" % up), hdr_text)
     emit._write(unit, unit_text)
     if field_gen is not None and field_gen[3] == d:
         emit._write(os.path.join(d, "params_%s_w32.h" % field), field_text)      # (what generate_w32 writes: the curve parts compile beside it)
     if emit_only:
         return out
-    field_job = None
-    if field_gen is not None:
-        fg = lambda: generate_w32(field_gen[0], family=field_gen[1], name=field, radix=field_gen[2], plugin_dir=field_gen[3], verbose=verbose)
-        field_job = fg if not os.path.exists(plugin_path(field, field_gen[3], 32)) else None
-    if not force and os.path.exists(lib) and os.path.exists(meta) and field_job is None:
-        try:
-            if json.load(open(meta)).get("hash") == key:
-                return out
-        except (ValueError, OSError):
-            pass
-    if not os.path.exists(HIPCC):
-        raise GenerateError("%s not found: generating a curve needs the ROCm compiler (there is no CPU path)" % HIPCC)
-    if not os.path.exists(os.path.join(HERE, "libmodarith_amd.so")):
-        raise GenerateError("%s is missing: build it first (python -m modarith_amd.build); plug-ins link against it" % os.path.join(HERE, "libmodarith_amd.so"))
-    if verbose:
-        print("[modarith_amd] hipcc %s (three parts) -> %s" % (os.path.basename(unit), os.path.basename(lib)), flush=True)
-    tmp = ".%d.tmp" % os.getpid()
-    inc_dirs = ["-I", os.path.join(HERE, "csrc", "generated"), "-I", os.path.join(HERE, "csrc"), "-I", os.path.join(os.path.dirname(HERE), "include"), "-I", d, "-I", PLUGIN_DIR]
-    parts = [(part, os.path.join(d, "capi_curve_%s_ecn_%s.o" % (stem, nm))) for part, nm in ((1, "mul"), (2, "mul2"), (3, "rest"))]
-    timeout = int(os.environ.get("MA_BUILD_TIMEOUT", "1500"))
-
-    def compile_part(t):
-        subprocess.run([HIPCC] + list(FLAGS) + inc_dirs + ["-DMA_CURVE_PART=%d" % t[0], "-c", unit, "-o", t[1] + tmp], check=True, timeout=timeout)
-
-    with cf.ThreadPoolExecutor(max_workers=4) as ex:
-        jobs = [ex.submit(compile_part, t) for t in parts] + ([ex.submit(field_job)] if field_job else [])
-        for j in jobs:
-            j.result()
-    subprocess.check_call([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib + tmp] + [o + tmp for _, o in parts]
-                          + ["-L", HERE, "-l:libmodarith_amd.so", "-Wl,-rpath,$ORIGIN/" + os.path.relpath(HERE, d), "-Wl,-rpath," + HERE])
-    with open(meta + tmp, "w") as f:
-        json.dump({"curve": up, "wl": 32, "kind": kind, "field": field, "a": a, "b": hex(b) if b >= 0 else "-" + hex(-b), "order": hex(order), "cof": cof,
-                   "gx": hex(gx), "gy": hex(gy), "nlimbs": fp.nlimbs, "radix": fp.radix, "family": fp.family, "nbytes": fp.nbytes, "mul_wps": wps,
-                   "hash": key}, f, indent=1)
-    for _, o in parts:
-        os.replace(o + tmp, o)
-    os.replace(lib + tmp, lib)
-    os.replace(meta + tmp, meta)
-    out.built = True
+    jobs = []
+    if field_gen is not None and not os.path.exists(plugin_path(field, field_gen[3], 32)):
+        # the field's plug-in is not there yet: it is generated beside the curve's parts, and the curve is built whatever its metadata says
+        jobs = [lambda: generate_w32(field_gen[0], family=field_gen[1], name=field, radix=field_gen[2], plugin_dir=field_gen[3], verbose=verbose)]
+    record = dict(_curve_record(c, kind, a, b, cof, fp), wl=32, radix=fp.radix, family=fp.family, mul_wps=wps)
+    units = [(unit, os.path.join(d, "capi_curve_%s_ecn_%s.o" % (stem, nm)), ["-DMA_CURVE_PART=%d" % part]) for part, nm in ((1, "mul"), (2, "mul2"), (3, "rest"))]
+    out.built = build_plugin(d, lib, meta, record, key_of(hdr_text, unit_text, field_text), units, "curve", force or bool(jobs), verbose, jobs, GenerateError)
     return out
 
 
@@ -518,7 +410,6 @@ def generate_ladder(name: str, field: str, a24: int, cof: int, twist_secure: boo
     modpro + modinv, little-endian Nbytes records).  Only the TWIST_SECURE branch of rfc7748.c:224-227 is built; records move as
     64-bit words, so Nbytes must be a multiple of 8.  Returns the plug-in's path."""
     from . import _lib
-    from .params import derive
     if not _TAG_RE.match(name) or name in _lib.LADDERS:
         raise GenerateError("%r: not a usable name (X25519 and X448 are built in)" % (name,))
     if not twist_secure:
@@ -528,14 +419,10 @@ def generate_ladder(name: str, field: str, a24: int, cof: int, twist_secure: boo
     if not 0 < a24 < (1 << 28):
         raise GenerateError("A24 must be a small positive integer: it is the `int` of modmli (rfc7748.c:209)")
     d = plugin_dir or PLUGIN_DIR
-    if field in _lib.PRIMES:
-        fp = derive(field)
-    elif os.path.exists(os.path.join(d, "%s.json" % field)):
-        fp = params_of_plugin(field, d)
-    elif os.path.exists(os.path.join(PLUGIN_DIR, "%s.json" % field)):
-        fp = params_of_plugin(field)
-    else:
+    found = find_field(field, d)
+    if found is None:
         raise GenerateError("field %r is neither built in nor generated: run generate() for it first" % (field,))
+    fp = found[0]
     if fp.nbytes % 8:
         raise GenerateError("%d-byte records: the ladder kernel moves records as 64-bit words" % fp.nbytes)
     sym = "rfc7748_%s" % name
@@ -564,31 +451,10 @@ def generate_ladder(name: str, field: str, a24: int, cof: int, twist_secure: boo
         "    s.d2h(bv, dv, NB);",
         "}", ""])
     os.makedirs(d, exist_ok=True)
-    unit, obj = os.path.join(d, "capi_ladder_%s.hip" % name), os.path.join(d, "capi_ladder_%s.o" % name)
-    lib, meta = ladder_plugin_path(name, d), os.path.join(d, "ladder_%s.json" % name)
-    from .build import ARCH, FLAGS, HIPCC, _stamp
-    key = hashlib.sha256((" ".join(FLAGS) + "\n" + unit_text + "\n" + emit.header_text(fp) + "\n" + _stamp()).encode()).hexdigest()
-    if not force and os.path.exists(lib) and os.path.exists(meta):
-        try:
-            if json.load(open(meta)).get("hash") == key:
-                return lib
-        except (ValueError, OSError):
-            pass
-    if not os.path.exists(HIPCC):
-        raise GenerateError("%s not found: generating a ladder needs the ROCm compiler (there is no CPU path)" % HIPCC)
+    unit, lib = os.path.join(d, "capi_ladder_%s.hip" % name), ladder_plugin_path(name, d)
     emit._write(unit, unit_text)
-    if verbose:
-        print("[modarith_amd] hipcc %s -> %s" % (os.path.basename(unit), os.path.basename(lib)), flush=True)
-    tmp = ".%d.tmp" % os.getpid()
-    inc_dirs = ["-I", os.path.join(HERE, "csrc", "generated"), "-I", os.path.join(HERE, "csrc"), "-I", os.path.join(os.path.dirname(HERE), "include"), "-I", PLUGIN_DIR, "-I", d]
-    subprocess.run([HIPCC] + list(FLAGS) + inc_dirs + ["-c", unit, "-o", obj + tmp], check=True, timeout=int(os.environ.get("MA_BUILD_TIMEOUT", "1500")))
-    subprocess.check_call([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib + tmp, obj + tmp, "-L", HERE, "-l:libmodarith_amd.so",
-                           "-Wl,-rpath,$ORIGIN/" + os.path.relpath(HERE, d), "-Wl,-rpath," + HERE])
-    with open(meta + tmp, "w") as f:
-        json.dump({"ladder": name, "field": field, "a24": a24, "cof": cof, "nbytes": fp.nbytes, "nbits": fp.n, "hash": key}, f, indent=1)
-    os.replace(obj + tmp, obj)
-    os.replace(lib + tmp, lib)
-    os.replace(meta + tmp, meta)
+    build_plugin(d, lib, os.path.join(d, "ladder_%s.json" % name), {"ladder": name, "field": field, "a24": a24, "cof": cof, "nbytes": fp.nbytes, "nbits": fp.n},
+                 key_of(unit_text, emit.header_text(fp)), [(unit, os.path.join(d, "capi_ladder_%s.o" % name), [])], "ladder", force, verbose, error=GenerateError)
     return lib
 
 
@@ -598,20 +464,20 @@ def generate_ladder(name: str, field: str, a24: int, cof: int, twist_secure: boo
 EXAMPLE_LADDERS = (dict(name="M383", field="PM383", a24=516287, cof=3), dict(name="T2519", field="2519", a24=12345, cof=3))
 
 
+def _scan(plugin_dir: Optional[str], prefix: str, lib_of):
+    """the metadata <prefix><X>.json of every plug-in of the directory whose shared object lib_of(<X>, directory) is present"""
+    d = plugin_dir or PLUGIN_DIR
+    for f in sorted(os.listdir(d)) if os.path.isdir(d) else []:
+        if f.startswith(prefix) and f.endswith(".json") and os.path.exists(lib_of(f[len(prefix):-5], d)):
+            try:
+                yield json.load(open(os.path.join(d, f)))
+            except ValueError:
+                continue
+
+
 def installed_curves(plugin_dir: Optional[str] = None, wl: int = 64) -> List[dict]:
     """metadata of every curve plug-in of word length wl whose shared object is present (curve_<CURVE>.json; 32: curve_<CURVE>_w32.json)"""
-    d = plugin_dir or PLUGIN_DIR
-    out = []
-    if os.path.isdir(d):
-        for f in sorted(os.listdir(d)):
-            if f.startswith("curve_") and f.endswith(".json") and os.path.exists(curve_plugin_path(f[6:-5], d)):
-                try:
-                    m = json.load(open(os.path.join(d, f)))
-                except ValueError:
-                    continue
-                if m.get("wl", 64) == wl:
-                    out.append(m)
-    return out
+    return [m for m in _scan(plugin_dir, "curve_", curve_plugin_path) if m.get("wl", 64) == wl]
 
 
 # curves the test-suite generates: Curve1174 (Bernstein-Hamburg-Krasnova-Lange: x^2 + y^2 = 1 - 1174 x^2 y^2 over 2^251 - 9, the generated
@@ -630,28 +496,16 @@ EXAMPLE_CURVES = (
 
 
 def installed(plugin_dir: Optional[str] = None, wl: int = 64) -> List[dict]:
-    """metadata of every field plug-in of word length wl whose shared object is present (64: the default; 32: generate_w32's)"""
-    d = plugin_dir or PLUGIN_DIR
-    out = []
-    if os.path.isdir(d):
-        for f in sorted(os.listdir(d)):
-            if f.endswith(".json") and os.path.exists(plugin_path(f[:-5], d)):      # (<TAG>_w32.json sits next to libmodarith_amd_<TAG>_w32.so)
-                try:
-                    m = json.load(open(os.path.join(d, f)))
-                except ValueError:
-                    continue
-                if "tag" in m and m.get("wl", 64) == wl:      # (the directory also holds the plug-ins of fused chains, modarith_amd/fuse.py)
-                    out.append(m)
-    return out
+    """metadata of every field plug-in of word length wl whose shared object is present (64: the default; 32: generate_w32's, whose
+    <TAG>_w32.json sits next to libmodarith_amd_<TAG>_w32.so).  The directory also holds the plug-ins of curves, ladders and fused
+    chains (modarith_amd/fuse.py): theirs have no "tag"."""
+    return [m for m in _scan(plugin_dir, "", plugin_path) if "tag" in m and m.get("wl", 64) == wl]
 
 
 def params_of_plugin(tag: str, plugin_dir: Optional[str] = None, wl: int = 64) -> FieldParams:
     """FieldParams of an installed plug-in, re-derived from its recorded modulus / family / radix"""
-    d = plugin_dir or PLUGIN_DIR
-    meta = json.load(open(os.path.join(d, "%s%s.json" % (tag, "" if wl == 64 else "_w32"))))
-    p = int(meta["p"], 16)
-    fp = (derive_pseudo if meta["family"] == "pseudo" else derive_monty)(tag, p, meta["radix"], wl)
-    return fp
+    meta = json.load(open(_meta_path(tag, plugin_dir, wl)))
+    return (derive_pseudo if meta["family"] == "pseudo" else derive_monty)(tag, int(meta["p"], 16), meta["radix"], wl)
 
 
 def report(fp: FieldParams) -> str:
@@ -743,11 +597,8 @@ def main(argv: List[str]) -> int:
             print("%-12s %-11s over %-8s a = %d, b = %s" % (m["curve"], m["kind"], m["field"], m["a"], m["b"]))
         for m in installed_curves(wl=32):
             print("%-12s %-11s over %-8s a = %d, b = %s   (32-bit words, %d limbs)" % (m["curve"], m["kind"], m["field"], m["a"], m["b"], m["nlimbs"]))
-        d = PLUGIN_DIR
-        for f in sorted(os.listdir(d)) if os.path.isdir(d) else []:
-            if f.startswith("ladder_") and f.endswith(".json") and os.path.exists(ladder_plugin_path(f[7:-5])):
-                m = json.load(open(os.path.join(d, f)))
-                print("%-12s ladder      over %-8s A24 = %d, COF = %d" % (m["ladder"], m["field"], m["a24"], m["cof"]))
+        for m in _scan(None, "ladder_", ladder_plugin_path):
+            print("%-12s ladder      over %-8s A24 = %d, COF = %d" % (m["ladder"], m["field"], m["a24"], m["cof"]))
         return 0
     if args and args[0] == "ladder":
         # python -m modarith_amd.generate ladder <name> <field> <A24> <COF>
