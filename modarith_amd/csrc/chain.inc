@@ -1,0 +1,191 @@
+// modarith_amd/csrc/chain.inc -- what every fused chain (modarith_amd/fuse.py) has in common: the kernels around the chain and the bodies
+// of its C entry points, at either word length (MA_WL: kernels.h / kernels32.h).  The generated unit includes this file ONCE, inside its
+// own anonymous namespace, after the pieces that depend on the chain:
+//   #define CHAIN_SYMBOL "chain_<name>_<TAG>"                             what the entry points are called, without _batch / _aos
+//   using namespace ma | ma32;  using P = ...;
+//   constexpr int NIN, NOUT, NSEL;  constexpr bool HEAVY;                 arrays in and out, selectors; a chain at one element per lane
+//   constexpr int EPT_CAP, CBLOCK;                                        word length 32 only: widest width of the build, workgroup size
+//   #define CHAIN_AOS_IMAGES k                                            word length 64 only: LDS images of the element-major kernel
+//   #define CHAIN_KERNEL_ATTR __attribute__((...))                        optional: an occupancy hint on k_chain
+//   template <class F> MA_DEV void body(v0, ..., s0, ...);                the chain on one element's registers
+//   template <int EPT, class IO> MA_DEV void chain_step(IO io);           EPT elements of a lane: io.load(i, v_i) per input, io.sel(k, s_k)
+//                                                                         per selector, the vote, body, io.store(k, v_o) per output
+// and then defines its `extern "C"` symbols over chain_batch() and chain_aos().  Editing this file rebuilds every chain (generate.key_of
+// hashes all of csrc/).
+#if MA_WL == 32
+using ma::check_launch;         // (the host helpers of capi_common.h; the 64-bit unit has all of namespace ma in scope)
+using ma::grid_for;
+using ma::set_error;
+#endif
+#if MA_WL == 64
+constexpr int EPT_CAP = HEAVY ? 1 : 2;   // widest access of a call in elements per lane (2 = 16 bytes, 1 = 8)
+constexpr int EPT_BUILT = 2;             // (both widths are compiled for every 64-bit chain, a HEAVY one included: as the units always were)
+constexpr int CBLOCK = BLOCK;            // workgroup size
+#else
+constexpr int EPT_BUILT = EPT_CAP;       // wider kernels are not instantiated
+#endif
+static_assert(EPT_CAP == 1 || EPT_CAP == 2 || (EPT_CAP == 4 && MA_WL == 32), "one or two elements per lane, four of 32-bit limbs");
+static_assert(!HEAVY || EPT_CAP == 1, "the long chains run one element per lane");
+#ifndef CHAIN_KERNEL_ATTR
+#define CHAIN_KERNEL_ATTR
+#endif
+struct Args { const spint* in[NIN]; spint* out[NOUT]; const int* sel[NSEL > 0 ? NSEL : 1]; };
+
+// ---- limb-interleaved batches: load_soa / store_soa at lane t, EPT consecutive elements
+template <int EPT> struct SoaIO {
+    const Args& A; Ld L; size_t t;
+    MA_DEV void load(int i, spint (*v)[P::N]) const { load_soa<P, EPT>(A.in[i], L, t, v); }
+    MA_DEV void sel(int k, int* s) const { static_for<0, EPT>([&](auto E) { s[E] = A.sel[k][(size_t)EPT * t + E]; }); }
+    MA_DEV void store(int k, spint (*v)[P::N]) const { store_soa<P, EPT>(A.out[k], L, t, v); }
+};
+template <int EPT>
+__global__ __launch_bounds__(CBLOCK) CHAIN_KERNEL_ATTR void k_chain(Args A, size_t nthreads, Ld L) {
+    for (size_t t = (size_t)blockIdx.x * CBLOCK + threadIdx.x; t < nthreads; t += (size_t)gridDim.x * CBLOCK) chain_step<EPT>(SoaIO<EPT>{A, L, t});
+}
+
+// in[0 .. NIN): element batches; in[NIN .. NIN + NSEL): int32 selector arrays, one entry per element
+int chain_batch(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) {
+    if (n == 0) return 0;
+    Ld L(ld);
+    if (ld < n) {
+        if (ld < 128 || (ld & (ld - 1)) != 0) { set_error(CHAIN_SYMBOL "_batch: a limb stride below n selects the tiled layout and must be a power of two >= 128"); return (int)hipErrorInvalidValue; }
+        L = Ld(ld, (unsigned)__builtin_ctzll((unsigned long long)ld));
+    }
+    Args A;
+    uintptr_t addr = 0;
+    for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; addr |= reinterpret_cast<uintptr_t>(in[i]); }
+    for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; addr |= reinterpret_cast<uintptr_t>(out[i]); }
+    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + i];
+    hipStream_t s = (hipStream_t)stream;
+    const bool tiled = L.s != 63;
+    // elements per lane (the rules of the library's pick_ept, capi_field.inc): e elements need n >= e, a stride that is a multiple of e
+    // and rows aligned to e words; what is left over (fewer than e elements) runs one element per lane at its own address, flat stride
+    size_t e = EPT_CAP;
+    while (e > 1 && !(n >= e && ld % e == 0 && (addr & (e * sizeof(spint) - 1)) == 0)) e /= 2;
+    const size_t nt = n / e, done = nt * e;
+    if constexpr (EPT_BUILT >= 4) if (e == 4) k_chain<4><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, nt, L);
+    if constexpr (EPT_BUILT >= 2) if (e == 2) k_chain<2><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, nt, L);
+    if (e == 1) k_chain<1><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, nt, L);
+    if (done < n) {
+        const size_t o = L.off<P::N>(done);
+        Args B;
+        for (int i = 0; i < NIN; i++) B.in[i] = A.in[i] + o;
+        for (int i = 0; i < NOUT; i++) B.out[i] = A.out[i] + o;
+        for (int i = 0; i < NSEL; i++) B.sel[i] = A.sel[i] + done;
+        k_chain<1><<<1, CBLOCK, 0, s>>>(B, n - done, Ld(L.ld));
+    }
+    return check_launch(CHAIN_SYMBOL "_batch");
+}
+
+#if defined(CHAIN_AOS_IMAGES) && CHAIN_AOS_IMAGES > 0
+// ---- element-major I/O: x[n][N] in, x[n][N] out (how the scalar callers of field.c hold their elements).  A workgroup of 256 lanes
+// takes a chunk of 512 elements; each array's chunk is one linear stretch of 512 N words, moved with 16-byte-per-lane coalesced accesses
+// and transposed through LDS (pitch N | 1 words: two-way bank conflicts at most; the pattern of capi_common.hip k_convert_lds, which is
+// why 64 KB hold fields of up to 14 limbs) into the lanes' registers -- elements 2t, 2t+1 -- and back.  The layout conversions on either
+// side of a chain (160 bytes of HBM traffic per element and array) disappear into the kernel.
+// CHAIN_AOS_IMAGES = NIN: one LDS image per input array while they fit 64 KB, so that every array's loads are issued before the first
+// barrier (measured against one shared image: X25519 0.577 -> 0.517 ms, X448 1.089 -> 1.038 ms); = 1 < NIN: one image, array by array.
+static_assert(CHAIN_AOS_IMAGES == 1 || CHAIN_AOS_IMAGES == NIN, "one image for all input arrays or one each");
+constexpr int CH = 512, SP = P::N | 1;
+MA_DEV void aos_load(const spint* aos, size_t cnt, spint* sh) {
+    const int t = threadIdx.x;
+    const size_t total = cnt * (size_t)P::N;
+    int e = (2 * t) / P::N, i = (2 * t) % P::N;
+    constexpr int de = CH / P::N, di = CH % P::N;
+    for (size_t w = 2 * (size_t)t; w < total; w += CH) {
+        int e1 = e, i1 = i + 1;
+        if (i1 == P::N) { i1 = 0; e1++; }
+        if (w + 1 < total) {
+            const spint2 x = __builtin_nontemporal_load(reinterpret_cast<const spint2*>(aos + w));
+            sh[e * SP + i] = x.x; sh[e1 * SP + i1] = x.y;
+        } else {
+            sh[e * SP + i] = aos[w];
+        }
+        e += de; i += di;
+        if (i >= P::N) { i -= P::N; e++; }
+    }
+}
+// every input array's chunk into its own image (a fold over the indices, not a static_for: a lambda around A costs the kernel registers)
+template <int... I> MA_DEV void aos_load_all(const Args& A, size_t c0, size_t cnt, spint* sh, std::integer_sequence<int, I...>) {
+    (aos_load(A.in[I] + c0 * (size_t)P::N, cnt, sh + I * CH * SP), ...);
+}
+MA_DEV void aos_regs(size_t cnt, const spint* sh, spint (*v)[P::N]) {
+    const int t = threadIdx.x;
+    static_for<0, 2>([&](auto E) {
+        const bool live = 2 * (size_t)t + E < cnt;         // lanes beyond the chunk's end compute on zeros (inside the limb contract)
+        static_for<0, P::N>([&](auto I) { v[E][I] = live ? sh[(2 * t + E) * SP + I] : 0; });
+    });
+}
+MA_DEV void aos_in(const spint* aos, size_t cnt, spint* sh, spint (*v)[P::N]) {
+    __syncthreads();                                  // the previous user of sh is done
+    aos_load(aos, cnt, sh);
+    __syncthreads();
+    aos_regs(cnt, sh, v);
+}
+MA_DEV void aos_out(spint* aos, size_t cnt, spint* sh, spint (*v)[P::N]) {
+    const int t = threadIdx.x;
+    const size_t total = cnt * (size_t)P::N;
+    __syncthreads();
+    static_for<0, 2>([&](auto E) { static_for<0, P::N>([&](auto I) { sh[(2 * t + E) * SP + I] = v[E][I]; }); });
+    __syncthreads();
+    int e = (2 * t) / P::N, i = (2 * t) % P::N;
+    constexpr int de = CH / P::N, di = CH % P::N;
+    for (size_t w = 2 * (size_t)t; w < total; w += CH) {
+        int e1 = e, i1 = i + 1;
+        if (i1 == P::N) { i1 = 0; e1++; }
+        if (w + 1 < total) {
+            spint2 x; x.x = sh[e * SP + i]; x.y = sh[e1 * SP + i1];
+            __builtin_nontemporal_store(x, reinterpret_cast<spint2*>(aos + w));
+        } else {
+            aos[w] = sh[e * SP + i];
+        }
+        e += de; i += di;
+        if (i >= P::N) { i -= P::N; e++; }
+    }
+}
+struct AosIO {                                        // two elements per lane: 2t, 2t + 1 of the chunk of cnt elements at c0
+    const Args& A; spint* sh; size_t c0, cnt, off;
+    MA_DEV void load(int i, spint (*v)[P::N]) const {
+        if constexpr (CHAIN_AOS_IMAGES == NIN) aos_regs(cnt, sh + i * CH * SP, v);        // (k_chain_aos has filled the images)
+        else aos_in(A.in[i] + off, cnt, sh, v);
+    }
+    MA_DEV void sel(int k, int* s) const {
+        const int t = threadIdx.x;
+        const int* d = A.sel[k] + c0;
+        static_for<0, 2>([&](auto E) { s[E] = (2 * (size_t)t + E < cnt) ? d[2 * (size_t)t + E] : 0; });
+    }
+    MA_DEV void store(int k, spint (*v)[P::N]) const { aos_out(A.out[k] + off, cnt, sh, v); }
+};
+__global__ __launch_bounds__(BLOCK) void k_chain_aos(Args A, size_t n) {
+    __shared__ spint sh[CHAIN_AOS_IMAGES * CH * SP];
+    for (size_t c0 = (size_t)blockIdx.x * CH; c0 < n; c0 += (size_t)gridDim.x * CH) {
+        const size_t cnt = (n - c0 < (size_t)CH) ? n - c0 : (size_t)CH;
+        if constexpr (CHAIN_AOS_IMAGES == NIN) {
+            __syncthreads();
+            aos_load_all(A, c0, cnt, sh, std::make_integer_sequence<int, NIN>());
+            __syncthreads();
+        }
+        chain_step<2>(AosIO{A, sh, c0, cnt, c0 * (size_t)P::N});
+    }
+}
+
+// element-major arrays spint x[n][Nlimbs] (16-byte aligned); in[NIN ..): int32 selector arrays as in the _batch form
+int chain_aos(const void* const* in, void* const* out, size_t n, void* stream) {
+    if (n == 0) return 0;
+    Args A;
+    bool al = true;
+    for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; al = al && aligned16(in[i]); }
+    for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; al = al && aligned16(out[i]); }
+    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + i];
+    if (!al) { set_error(CHAIN_SYMBOL "_aos: element-major arrays must be 16-byte aligned"); return (int)hipErrorInvalidValue; }
+    const size_t chunks = (n + CH - 1) / CH;
+    const size_t cap = (size_t)max_blocks_tiled();
+    k_chain_aos<<<(unsigned)(chunks < cap ? chunks : cap), BLOCK, 0, (hipStream_t)stream>>>(A, n);
+    return check_launch(CHAIN_SYMBOL "_aos");
+}
+#elif defined(CHAIN_AOS_IMAGES)
+int chain_aos(const void* const*, void* const*, size_t, void*) {        // more than 14 limbs: no kernel
+    set_error(CHAIN_SYMBOL "_aos: element-major I/O is built for fields of up to 14 limbs; convert with modarith_amd_aos_to_soa");
+    return (int)hipErrorInvalidValue;
+}
+#endif

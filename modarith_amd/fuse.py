@@ -242,283 +242,84 @@ class Chain:
                 L.append("    F::%s(v%d, v%d);" % (op, a, d))
         return L
 
-    def _source32(self, ept: Optional[int], waves: int, block: Optional[int]) -> str:
-        """the unit of the 32-bit word form: csrc/kernels32.h's load_soa / store_soa around body<Field<P>>, one product policy"""
-        P, nv = self.prime, self.nvals
-        heavy = any(o[0] in _HEAVY for o in self.ops)
-        cap = 1 if heavy else (ept or self.default_ept())
-        if cap not in (1, 2, 4):
-            raise ValueError("elements per lane at word length 32: 1, 2 or 4")
-        if not self.builtin:
-            cap = min(cap, emit.w32_ept_max(self.params.nlimbs))       # (the width a generated field's limb count leaves in registers)
-        block = block or W32_BLOCK_DEFAULT
-        if block not in (64, 128, 256):
-            raise ValueError("workgroup size: 64, 128 or 256")
-        args = ", ".join(["v%d[E]" % i for i in range(nv)] + ["s%d[E]" % k for k in range(self.nsel)])
-        L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s, 32-bit word form: %d inputs, %d operations, %d outputs." % (self.name, P, self.nin, len(self.ops), len(self.outs)),
-             '#include "%s"' % ("w32_%s.h" % P if self.builtin else "params_%s_w32.h" % P), '#include "modarith_amd_w32.h"', '#include "capi_common.h"', '#include "kernels32.h"', "",
-             "namespace {", "using namespace ma32;", "using ma::check_launch;", "using ma::grid_for;", "using ma::set_error;", "using P = ma32::P_%s_W32;" % P,
-             "constexpr int NIN = %d, NOUT = %d, NSEL = %d;" % (self.nin, len(self.outs), self.nsel),
-             "constexpr bool HEAVY = %s;   // an inversion, a progenitor or a square root in the chain: one element per lane" % ("true" if heavy else "false"),
-             "constexpr int EPT_CAP = %d;   // widest access of this build in elements per lane (4 = 16 bytes, 2 = 8, 1 = 4); wider kernels are not instantiated" % cap,
-             "constexpr int CBLOCK = %d;   // workgroup size" % block,
-             'static_assert(!HEAVY || EPT_CAP == 1, "the long chains run one element per lane");',
-             "struct Args { const spint* in[NIN]; spint* out[NOUT]; const int* sel[NSEL > 0 ? NSEL : 1]; };", "",
-             "// the chain on one element's registers; F = Field<P> (one product policy at this word length: no vote)",
-             "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i < self.nin else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)])]
-        L += self._body_lines()
-        L += ["}", "",
-              "template <int EPT>", "__global__ __launch_bounds__(CBLOCK) %svoid k_chain(Args A, size_t nthreads, Ld L) {" % ("__attribute__((amdgpu_waves_per_eu(%d, %d))) " % (waves, waves) if waves else ""),
-              "    for (size_t t = (size_t)blockIdx.x * CBLOCK + threadIdx.x; t < nthreads; t += (size_t)gridDim.x * CBLOCK) {",
-              "        " + " ".join("spint v%d[EPT][P::N];" % i for i in range(nv))]
-        L += ["        load_soa<P, EPT>(A.in[%d], L, t, v%d);" % (i, i) for i in range(self.nin)]
-        L += ["        int s%d[EPT]; static_for<0, EPT>([&](auto E) { s%d[E] = A.sel[%d][(size_t)EPT * t + E]; });" % (k, k, k) for k in range(self.nsel)]
-        L += ["        static_for<0, EPT>([&](auto E) { body<Field<P>>(%s); });" % args]
-        L += ["        store_soa<P, EPT>(A.out[%d], L, t, v%d);" % (k, o) for k, o in enumerate(self.outs)]
-        L += ["    }", "}", "}  // namespace", "",
-              'extern "C" int %s(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) {' % self.symbol,
-              "    // in[0 .. NIN): element batches of uint32_t limbs; in[NIN .. NIN + NSEL): int32 selector arrays, one entry per element",
-              "    if (n == 0) return 0;",
-              "    Ld L(ld);",
-              "    if (ld < n) {",
-              '        if (ld < 128 || (ld & (ld - 1)) != 0) { set_error("%s: a limb stride below n selects the tiled layout and must be a power of two >= 128"); return (int)hipErrorInvalidValue; }' % self.symbol,
-              "        L = Ld(ld, (unsigned)__builtin_ctzll((unsigned long long)ld));",
-              "    }",
-              "    Args A;",
-              "    uintptr_t addr = 0;",
-              "    for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; addr |= reinterpret_cast<uintptr_t>(in[i]); }",
-              "    for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; addr |= reinterpret_cast<uintptr_t>(out[i]); }",
-              "    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + i];",
-              "    hipStream_t s = (hipStream_t)stream;",
-              "    const bool tiled = L.s != 63;",
-              "    // elements per lane (the rules of the library's pick_ept): EPT elements need n >= EPT, a stride that is a multiple of EPT and",
-              "    // 4 * EPT-byte aligned rows; what is left over (fewer than EPT elements) runs one element per lane at its own address",
-              "    int ept = 1;",
-              "    if (EPT_CAP >= 4 && n >= 4 && ld % 4 == 0 && (addr & 15u) == 0) ept = 4;",
-              "    else if (EPT_CAP >= 2 && n >= 2 && ld % 2 == 0 && (addr & 7u) == 0) ept = 2;",
-              "    const size_t nt = n / ept, done = nt * ept;",
-              "    if constexpr (EPT_CAP >= 4) if (ept == 4) k_chain<4><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, nt, L);",
-              "    if constexpr (EPT_CAP >= 2) if (ept == 2) k_chain<2><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, nt, L);",
-              "    if (ept == 1) k_chain<1><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, nt, L);",
-              "    if (done < n) {",
-              "        const size_t o = L.off<P::N>(done);",
-              "        Args B;",
-              "        for (int i = 0; i < NIN; i++) B.in[i] = A.in[i] + o;",
-              "        for (int i = 0; i < NOUT; i++) B.out[i] = A.out[i] + o;",
-              "        for (int i = 0; i < NSEL; i++) B.sel[i] = A.sel[i] + done;",
-              "        k_chain<1><<<1, CBLOCK, 0, s>>>(B, n - done, Ld(L.ld));",
-              "    }",
-              '    return check_launch("%s");' % self.symbol,
-              "}", ""]
-        return "\n".join(L)
-
     def source(self, ept: Optional[int] = None, policy: str = "vote", waves: int = 0, block: Optional[int] = None) -> str:
-        """ept: elements per lane on aligned batches (2 = 16-byte accesses, 1 = 8-byte; at word length 32: 4 / 2 / 1 = 16 / 8 / 4 bytes);
+        """The unit: what depends on the chain -- constants, body<F> and chain_step<EPT, IO> -- around csrc/chain.inc, which holds the
+        kernels (k_chain<EPT>, k_chain_aos) and the bodies of the entry points for both word lengths.
+        ept: elements per lane on aligned batches (2 = 16-byte accesses, 1 = 8-byte; at word length 32: 4 / 2 / 1 = 16 / 8 / 4 bytes);
         None = the measured default.  block: workgroup size, word length 32 only"""
         if not self.nin or not self.outs:
             raise ValueError("a chain needs at least one input and one output")
-        if self.wl == 32:
+        P, nv, N, w32 = self.prime, self.nvals, self.params.nlimbs, self.wl == 32
+        if w32:
             if policy != "vote":
                 raise ValueError("word length 32 has one product policy: there is nothing to force")
-            return self._source32(ept, waves, block)
-        if block is not None:
-            raise ValueError("the workgroup size is a parameter of the 32-bit word form only")
-        P, nv = self.prime, self.nvals
-        L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s: %d inputs, %d operations, %d outputs." % (self.name, P, self.nin, len(self.ops), len(self.outs)),
-             '#include "params_%s.h"' % P, '#include "modarith_amd.h"', '#include "capi_common.h"', '#include "kernels.h"', "",
-             "namespace {", "using namespace ma;", "using P = ma::P_%s;" % P, "constexpr int NIN = %d, NOUT = %d;" % (self.nin, len(self.outs)),
-             "constexpr bool HEAVY = %s;   // one element per lane (8-byte accesses) on every batch: chains with an inversion, as the library's k_unary_heavy" % ("true" if (ept or self.default_ept()) == 1 else "false"),
-             "constexpr int NSEL = %d;" % self.nsel,
-             "struct Args { const spint* in[NIN]; spint* out[NOUT]; const int* sel[NSEL > 0 ? NSEL : 1]; };", "",
-             "// the chain on one element's registers; F = Field<P, FAST>",
-             "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i < self.nin else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)])]
+            heavy = any(o[0] in _HEAVY for o in self.ops)
+            cap = 1 if heavy else (ept or self.default_ept())
+            if cap not in (1, 2, 4):
+                raise ValueError("elements per lane at word length 32: 1, 2 or 4")
+            if not self.builtin:
+                cap = min(cap, emit.w32_ept_max(N))       # (the width a generated field's limb count leaves in registers)
+            block = block or W32_BLOCK_DEFAULT
+            if block not in (64, 128, 256):
+                raise ValueError("workgroup size: 64, 128 or 256")
+            head = ['#include "%s"' % ("w32_%s.h" % P if self.builtin else "params_%s_w32.h" % P), '#include "modarith_amd_w32.h"', '#include "capi_common.h"', '#include "kernels32.h"', "#include <utility>", "",
+                    "namespace {", "using namespace ma32;", "using P = ma32::P_%s_W32;" % P]
+            shape = ["constexpr int EPT_CAP = %d;   // widest access of this build in elements per lane (4 = 16 bytes, 2 = 8, 1 = 4); wider kernels are not instantiated" % cap,
+                     "constexpr int CBLOCK = %d;   // workgroup size" % block]
+        else:
+            if block is not None:
+                raise ValueError("the workgroup size is a parameter of the 32-bit word form only")
+            heavy = (ept or self.default_ept()) == 1      # (default_ept() is 1 where an operation of _HEAVY is in the chain)
+            # one LDS image per input array of the element-major kernel while they fit 64 KB (512 (N | 1) words each), else one shared
+            # image; none above 14 limbs, where a single image does not fit (as k_convert_lds)
+            images = 0 if N > 14 else self.nin if self.nin * 512 * (N | 1) * 8 <= 65536 else 1
+            head = ['#include "params_%s.h"' % P, '#include "modarith_amd.h"', '#include "capi_common.h"', '#include "kernels.h"', "#include <utility>", "",
+                    "namespace {", "using namespace ma;", "using P = ma::P_%s;" % P]
+            shape = ["#define CHAIN_AOS_IMAGES %d   // LDS images of the element-major kernel: one per input array, 1 = one shared image, 0 = no kernel (more than 14 limbs)" % images]
+        if waves:
+            shape.append("#define CHAIN_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(%d, %d)))" % (waves, waves))
+        args = ", ".join(["v%d[E]" % i for i in range(nv)] + ["s%d[E]" % k for k in range(self.nsel)])
+        if w32:
+            run = ["    static_for<0, EPT>([&](auto E) { body<Field<P>>(%s); });" % args]
+        else:
+            run = ["    bool fast = %s;" % ("true" if policy == "fast" else "false"),
+                   "    if constexpr (P::SPLIT > 0 && %s) {" % ("true" if policy == "vote" else "false"),
+                   "        bool ok = true;",
+                   "        static_for<0, EPT>([&](auto E) { ok = ok && " + " && ".join("in_split_contract<P>(v%d[E])" % i for i in range(self.nin)) + "; });",
+                   "        fast = __all(ok);",
+                   "    }",
+                   "    if (fast) {",
+                   "        static_for<0, EPT>([&](auto E) { body<Field<P, true>>(%s); });" % args,
+                   "    } else {",
+                   "        static_for<0, EPT>([&](auto E) { body<Field<P, false>>(%s); });" % args,
+                   "    }"]
+        L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s%s: %d inputs, %d operations, %d outputs; kernels and entry bodies: csrc/chain.inc"
+             % (self.name, P, ", 32-bit word form" if w32 else "", self.nin, len(self.ops), len(self.outs))]
+        L += head + ['#define CHAIN_SYMBOL "%s"   // the entry points: <this>_batch%s' % (self.symbol[:-6], "" if w32 else ", <this>_aos"),
+                     "constexpr int NIN = %d, NOUT = %d, NSEL = %d;" % (self.nin, len(self.outs), self.nsel),
+                     "constexpr bool HEAVY = %s;   // one element per lane on every batch: an inversion, a progenitor or a square root in the chain%s"
+                     % ("true" if heavy else "false", "" if w32 else ", or build(ept=1)")] + shape
+        L += ["", "// the chain on one element's registers; F = %s" % ("Field<P> (one product policy at this word length: no vote)" if w32 else "Field<P, FAST>"),
+              "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i < self.nin else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)])]
         L += self._body_lines()
-        L += ["}", "",
-              "template <int EPT>", "__global__ __launch_bounds__(BLOCK) %svoid k_chain(Args A, size_t nthreads, Ld L) {" % ("__attribute__((amdgpu_waves_per_eu(%d, %d))) " % (waves, waves) if waves else "")]
-        votel = ["bool fast = %s;" % ("true" if policy == "fast" else "false"),
-                 "if constexpr (P::SPLIT > 0 && %s) {" % ("true" if policy == "vote" else "false"),
-                 "    bool ok = true;",
-                 "    static_for<0, EPT>([&](auto E) { ok = ok && " + " && ".join("in_split_contract<P>(v%d[E])" % i for i in range(self.nin)) + "; });",
-                 "    fast = __all(ok);",
-                 "}",
-                 "if (fast) {",
-                 "    static_for<0, EPT>([&](auto E) { body<Field<P, true>>(%s); });" % ", ".join(["v%d[E]" % i for i in range(nv)] + ["s%d[E]" % k for k in range(self.nsel)]),
-                 "} else {",
-                 "    static_for<0, EPT>([&](auto E) { body<Field<P, false>>(%s); });" % ", ".join(["v%d[E]" % i for i in range(nv)] + ["s%d[E]" % k for k in range(self.nsel)]),
-                 "}"]
-        L += ["    for (size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x; t < nthreads; t += (size_t)gridDim.x * BLOCK) {",
-              "        " + " ".join("spint v%d[EPT][P::N];" % i for i in range(nv))]
-        L += ["        load_soa<P, EPT>(A.in[%d], L, t, v%d);" % (i, i) for i in range(self.nin)]
-        L += ["        int s%d[EPT]; static_for<0, EPT>([&](auto E) { s%d[E] = A.sel[%d][(size_t)EPT * t + E]; });" % (k, k, k) for k in range(self.nsel)]
-        L += ["        " + l for l in votel]
-        L += ["        store_soa<P, EPT>(A.out[%d], L, t, v%d);" % (k, o) for k, o in enumerate(self.outs)]
-        L += ["    }", "}"]
-        L += self._aos_kernel(votel)
-        L += ["}  // namespace", "",
-              'extern "C" int %s(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) {' % self.symbol,
-              "    // in[0 .. NIN): element batches; in[NIN .. NIN + NSEL): int32 selector arrays, one entry per element",
-              "    if (n == 0) return 0;",
-              "    Ld L(ld);",
-              "    if (ld < n) {",
-              '        if (ld < 128 || (ld & (ld - 1)) != 0) { set_error("%s: a limb stride below n selects the tiled layout and must be a power of two >= 128"); return (int)hipErrorInvalidValue; }' % self.symbol,
-              "        L = Ld(ld, (unsigned)__builtin_ctzll((unsigned long long)ld));",
-              "    }",
-              "    Args A;",
-              "    bool al = ld % 2 == 0;",
-              "    for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; al = al && aligned16(in[i]); }",
-              "    for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; al = al && aligned16(out[i]); }",
-              "    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + i];",
-              "    hipStream_t s = (hipStream_t)stream;",
-              "    const bool tiled = L.s != 63;",
-              "    if (n >= 2 && al && !HEAVY) {",
-              "        size_t nt = n / 2;",
-              "        k_chain<2><<<grid_for(nt, BLOCK, tiled), BLOCK, 0, s>>>(A, nt, L);",
-              "        if (n & 1) {                                  // the odd element out: one lane on the 8-byte path, at its own address",
-              "            const size_t o = L.off<P::N>(n - 1);",
-              "            Args B;",
-              "            for (int i = 0; i < NIN; i++) B.in[i] = A.in[i] + o;",
-              "            for (int i = 0; i < NOUT; i++) B.out[i] = A.out[i] + o;",
-              "            for (int i = 0; i < NSEL; i++) B.sel[i] = A.sel[i] + (n - 1);",
-              "            k_chain<1><<<1, BLOCK, 0, s>>>(B, 1, Ld(L.ld));",
-              "        }",
-              "    } else {",
-              "        k_chain<1><<<grid_for(n, BLOCK, tiled), BLOCK, 0, s>>>(A, n, L);",
-              "    }",
-              '    return check_launch("%s");' % self.symbol,
-              "}", ""]
-        L += self._aos_entry()
-        return "\n".join(L)
+        L += ["}", "", "// EPT elements of a lane through the chain; io is how the calling kernel of csrc/chain.inc reaches them in memory",
+              "template <int EPT, class IO> MA_DEV void chain_step(IO io) {",
+              "    " + " ".join("spint v%d[EPT][P::N];" % i for i in range(nv))]
+        L += ["    io.load(%d, v%d);" % (i, i) for i in range(self.nin)]
+        L += ["    int s%d[EPT]; io.sel(%d, s%d);" % (k, k, k) for k in range(self.nsel)]
+        L += run
+        L += ["    io.store(%d, v%d);" % (k, o) for k, o in enumerate(self.outs)]
+        L += ["}", '#include "chain.inc"', "}  // namespace", "",
+              'extern "C" int %s(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) { return chain_batch(in, out, n, ld, stream); }' % self.symbol]
+        if not w32:
+            L += ['extern "C" int %s(const void* const* in, void* const* out, size_t n, void* stream) { return chain_aos(in, out, n, stream); }' % self.aos_symbol]
+        return "\n".join(L + [""])
 
     @property
     def aos_symbol(self) -> str:
         if self.wl == 32:
             raise ValueError("the element-major entry is not built at word length 32: convert with modarith_amd_w32_aos_to_soa and call %s" % self.symbol)
         return "chain_%s_%s_aos" % (self.name, self.prime)
-
-    def _aos_kernel(self, votel: List[str]) -> List[str]:
-        """The same chain over ELEMENT-MAJOR arrays (`spint x[n][Nlimbs]`, how the scalar callers of field.c hold their elements): a
-        workgroup of 256 lanes takes a chunk of 512 elements; each array's chunk is one linear stretch of 512 N words, moved with
-        16-byte-per-lane coalesced accesses and transposed through LDS (pitch N | 1 words: two-way bank conflicts at most) into the
-        lanes' registers -- elements 2t, 2t+1 -- and back.  The layout conversions on either side of a chain (aos_to_soa before,
-        soa_to_aos after: 160 bytes of HBM traffic per element and array) disappear into the kernel."""
-        nv, N = self.nvals, self.params.nlimbs
-        if N > 14:                                    # 512 (N | 1) words of LDS per workgroup: 64 KB hold up to 14 limbs (as k_convert_lds)
-            return []
-        L = ["", "// ---- element-major I/O: x[n][N] in, x[n][N] out, transposed through LDS (the pattern of capi_common.hip k_convert_lds)",
-             "constexpr int CH = 512, SP = P::N | 1;",
-             "static __device__ __forceinline__ void aos_in(const spint* aos, size_t cnt, spint* sh, spint (*v)[P::N]) {",
-             "    const int t = threadIdx.x;",
-             "    const size_t total = cnt * (size_t)P::N;",
-             "    int e = (2 * t) / P::N, i = (2 * t) % P::N;",
-             "    constexpr int de = CH / P::N, di = CH % P::N;",
-             "    __syncthreads();                                  // the previous user of sh is done",
-             "    for (size_t w = 2 * (size_t)t; w < total; w += CH) {",
-             "        int e1 = e, i1 = i + 1;",
-             "        if (i1 == P::N) { i1 = 0; e1++; }",
-             "        if (w + 1 < total) {",
-             "            const spint2 x = __builtin_nontemporal_load(reinterpret_cast<const spint2*>(aos + w));",
-             "            sh[e * SP + i] = x.x; sh[e1 * SP + i1] = x.y;",
-             "        } else {",
-             "            sh[e * SP + i] = aos[w];",
-             "        }",
-             "        e += de; i += di;",
-             "        if (i >= P::N) { i -= P::N; e++; }",
-             "    }",
-             "    __syncthreads();",
-             "    static_for<0, 2>([&](auto E) {",
-             "        const bool live = 2 * (size_t)t + E < cnt;         // lanes beyond the chunk's end compute on zeros (inside the limb contract)",
-             "        static_for<0, P::N>([&](auto I) { v[E][I] = live ? sh[(2 * t + E) * SP + I] : 0; });",
-             "    });",
-             "}",
-             "static __device__ __forceinline__ void aos_load(const spint* aos, size_t cnt, spint* sh) {",
-             "    const int t = threadIdx.x;",
-             "    const size_t total = cnt * (size_t)P::N;",
-             "    int e = (2 * t) / P::N, i = (2 * t) % P::N;",
-             "    constexpr int de = CH / P::N, di = CH % P::N;",
-             "    for (size_t w = 2 * (size_t)t; w < total; w += CH) {",
-             "        int e1 = e, i1 = i + 1;",
-             "        if (i1 == P::N) { i1 = 0; e1++; }",
-             "        if (w + 1 < total) {",
-             "            const spint2 x = __builtin_nontemporal_load(reinterpret_cast<const spint2*>(aos + w));",
-             "            sh[e * SP + i] = x.x; sh[e1 * SP + i1] = x.y;",
-             "        } else {",
-             "            sh[e * SP + i] = aos[w];",
-             "        }",
-             "        e += de; i += di;",
-             "        if (i >= P::N) { i -= P::N; e++; }",
-             "    }",
-             "}",
-             "static __device__ __forceinline__ void aos_regs(size_t cnt, const spint* sh, spint (*v)[P::N]) {",
-             "    const int t = threadIdx.x;",
-             "    static_for<0, 2>([&](auto E) {",
-             "        const bool live = 2 * (size_t)t + E < cnt;",
-             "        static_for<0, P::N>([&](auto I) { v[E][I] = live ? sh[(2 * t + E) * SP + I] : 0; });",
-             "    });",
-             "}",
-             "static __device__ __forceinline__ void aos_out(spint* aos, size_t cnt, spint* sh, spint (*v)[P::N]) {",
-             "    const int t = threadIdx.x;",
-             "    const size_t total = cnt * (size_t)P::N;",
-             "    __syncthreads();",
-             "    static_for<0, 2>([&](auto E) { static_for<0, P::N>([&](auto I) { sh[(2 * t + E) * SP + I] = v[E][I]; }); });",
-             "    __syncthreads();",
-             "    int e = (2 * t) / P::N, i = (2 * t) % P::N;",
-             "    constexpr int de = CH / P::N, di = CH % P::N;",
-             "    for (size_t w = 2 * (size_t)t; w < total; w += CH) {",
-             "        int e1 = e, i1 = i + 1;",
-             "        if (i1 == P::N) { i1 = 0; e1++; }",
-             "        if (w + 1 < total) {",
-             "            spint2 x; x.x = sh[e * SP + i]; x.y = sh[e1 * SP + i1];",
-             "            __builtin_nontemporal_store(x, reinterpret_cast<spint2*>(aos + w));",
-             "        } else {",
-             "            aos[w] = sh[e * SP + i];",
-             "        }",
-             "        e += de; i += di;",
-             "        if (i >= P::N) { i -= P::N; e++; }",
-             "    }",
-             "}",
-             "__global__ __launch_bounds__(BLOCK) void k_chain_aos(Args A, size_t n) {",
-             "    __shared__ spint sh[CH * SP];",
-             "    constexpr int EPT = 2;",
-             "    const int t = threadIdx.x;",
-             "    (void)t;",
-             "    for (size_t c0 = (size_t)blockIdx.x * CH; c0 < n; c0 += (size_t)gridDim.x * CH) {",
-             "        const size_t cnt = (n - c0 < (size_t)CH) ? n - c0 : (size_t)CH;",
-             "        " + " ".join("spint v%d[EPT][P::N];" % i for i in range(nv))]
-        if getattr(self, "aos_multi", self.nin * 512 * (N | 1) * 8 <= 65536):
-            # one LDS image per input array while they fit 64 KB: every array's loads are issued before the first barrier
-            # (measured against one shared image in round 3: X25519 0.577 -> 0.517 ms, X448 1.089 -> 1.038 ms)
-            L = [l.replace("__shared__ spint sh[CH * SP];", "__shared__ spint sh[%d * CH * SP];" % self.nin) for l in L]
-            L += ["        __syncthreads();"]
-            L += ["        aos_load(A.in[%d] + c0 * (size_t)P::N, cnt, sh + %d * CH * SP);" % (i, i) for i in range(self.nin)]
-            L += ["        __syncthreads();"]
-            L += ["        aos_regs(cnt, sh + %d * CH * SP, v%d);" % (i, i) for i in range(self.nin)]
-        else:
-            L += ["        aos_in(A.in[%d] + c0 * (size_t)P::N, cnt, sh, v%d);" % (i, i) for i in range(self.nin)]
-        L += ["        int s%d[EPT]; static_for<0, EPT>([&](auto E) { s%d[E] = (2 * (size_t)t + E < cnt) ? A.sel[%d][c0 + 2 * (size_t)t + E] : 0; });" % (k, k, k) for k in range(self.nsel)]
-        L += ["        " + l for l in votel]
-        L += ["        aos_out(A.out[%d] + c0 * (size_t)P::N, cnt, sh, v%d);" % (k, o) for k, o in enumerate(self.outs)]
-        L += ["    }", "}"]
-        return L
-
-    def _aos_entry(self) -> List[str]:
-        if self.params.nlimbs > 14:
-            return ['extern "C" int %s(const void* const*, void* const*, size_t, void*) {' % self.aos_symbol,
-                    '    set_error("%s: element-major I/O is built for fields of up to 14 limbs; convert with modarith_amd_aos_to_soa");' % self.aos_symbol,
-                    "    return (int)hipErrorInvalidValue;", "}", ""]
-        return ['extern "C" int %s(const void* const* in, void* const* out, size_t n, void* stream) {' % self.aos_symbol,
-                "    // element-major arrays spint x[n][Nlimbs] (16-byte aligned); in[NIN ..): int32 selector arrays as in the _batch form",
-                "    if (n == 0) return 0;",
-                "    Args A;",
-                "    bool al = true;",
-                "    for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; al = al && aligned16(in[i]); }",
-                "    for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; al = al && aligned16(out[i]); }",
-                "    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + i];",
-                '    if (!al) { set_error("%s: element-major arrays must be 16-byte aligned"); return (int)hipErrorInvalidValue; }' % self.aos_symbol,
-                "    const size_t chunks = (n + CH - 1) / CH;",
-                "    const size_t cap = (size_t)max_blocks_tiled();",
-                "    k_chain_aos<<<(unsigned)(chunks < cap ? chunks : cap), BLOCK, 0, (hipStream_t)stream>>>(A, n);",
-                '    return check_launch("%s");' % self.aos_symbol,
-                "}", ""]
 
     # ------------------------------------------------------------------ building the plug-in
     def lib_path(self, plugin_dir: Optional[str] = None) -> str:
@@ -552,6 +353,25 @@ class FusedChain:
         self.fn.restype = ctypes.c_int
         self._fields = {}
 
+    def _split(self, inputs, what: str):
+        ch = self.chain
+        if len(inputs) != ch.nin + ch.nsel:
+            raise ValueError("chain %s takes %d element %s followed by %d int32 selector arrays" % (ch.name, ch.nin, what, ch.nsel))
+        return inputs[:ch.nin], inputs[ch.nin:]
+
+    def _run(self, fn, symbol: str, elems, sels, outs, n: int, *ld, device=None):
+        """what both entries share: the selector check, the pointer arrays and the call on the current stream of the batches' device"""
+        import torch
+        for d in sels:
+            if d.dtype != torch.int32 or d.numel() != n or not d.is_cuda or not d.is_contiguous() or (device is not None and d.device != device):
+                raise ValueError("selectors are contiguous int32 device tensors with one 0/1 entry per element")
+        dev = device if device is not None else elems[0].device
+        ins = (ctypes.c_void_p * (len(elems) + len(sels)))(*[t.data_ptr() for t in list(elems) + list(sels)])
+        ous = (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
+        with torch.cuda.device(dev):
+            _lib.check(fn(ins, ous, n, *ld, torch.cuda.current_stream(dev).cuda_stream), symbol)
+        return tuple(outs)
+
     def aos(self, *inputs, out: Optional[Sequence] = None):
         """the same chain over element-major device arrays int64 [n, Nlimbs] (`spint x[n][Nlimbs]`, how CPU callers of field.c hold
         elements): no aos_to_soa / soa_to_aos passes around it; selectors follow the element arrays as in __call__"""
@@ -560,33 +380,21 @@ class FusedChain:
         N = ch.params.nlimbs
         if ch.wl == 32:
             raise ValueError("the element-major entry is not built at word length 32: convert with modarith_amd_w32_aos_to_soa and call %s" % ch.symbol)
-        if len(inputs) != ch.nin + ch.nsel:
-            raise ValueError("chain %s takes %d element arrays followed by %d int32 selector arrays" % (ch.name, ch.nin, ch.nsel))
-        elems, sels = inputs[:ch.nin], inputs[ch.nin:]
+        elems, sels = self._split(inputs, "arrays")
         n = elems[0].shape[0]
         outs = list(out) if out is not None else [torch.empty_like(elems[0]) for _ in ch.outs]
         for t in list(elems) + outs:
             if t.dtype != torch.int64 or t.dim() != 2 or tuple(t.shape) != (n, N) or not t.is_cuda or not t.is_contiguous():
                 raise ValueError("expected contiguous int64 device tensors of shape [n, %d]" % N)
-        for d in sels:
-            if d.dtype != torch.int32 or d.numel() != n or not d.is_cuda or not d.is_contiguous():
-                raise ValueError("selectors are contiguous int32 device tensors with one 0/1 entry per element")
         fn = getattr(self.lib, ch.aos_symbol)
         fn.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_void_p]
         fn.restype = ctypes.c_int
-        ins = (ctypes.c_void_p * (ch.nin + ch.nsel))(*[t.data_ptr() for t in list(elems) + list(sels)])
-        ous = (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
-        with torch.cuda.device(elems[0].device):
-            _lib.check(fn(ins, ous, n, torch.cuda.current_stream(elems[0].device).cuda_stream), ch.aos_symbol)
-        return tuple(outs)
+        return self._run(fn, ch.aos_symbol, elems, sels, outs, n)
 
     def __call__(self, *inputs, out: Optional[Sequence] = None, device=None):
-        import torch
         from .field import Field
         ch = self.chain
-        if len(inputs) != ch.nin + ch.nsel:
-            raise ValueError("chain %s takes %d element batches followed by %d int32 selector arrays" % (ch.name, ch.nin, ch.nsel))
-        inputs, sels = inputs[:ch.nin], inputs[ch.nin:]
+        inputs, sels = self._split(inputs, "batches")
         dev = device if device is not None else inputs[0].device
         F = self._fields.get(dev)
         if F is None:                                  # binding a Field derives the prime's constants: once per device, not per call
@@ -595,14 +403,7 @@ class FusedChain:
         if len(outs) != len(ch.outs):
             raise ValueError("chain %s has %d outputs" % (ch.name, len(ch.outs)))
         n = F._chk(*inputs, *outs)
-        for d in sels:
-            if d.dtype != torch.int32 or d.numel() != n or not d.is_cuda or not d.is_contiguous() or d.device != F.device:
-                raise ValueError("selectors are contiguous int32 device tensors with one 0/1 entry per element")
-        ins = (ctypes.c_void_p * (ch.nin + ch.nsel))(*[t.data_ptr() for t in list(inputs) + list(sels)])
-        ous = (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
-        with torch.cuda.device(F.device):
-            _lib.check(self.fn(ins, ous, n, F._ld(inputs[0]), torch.cuda.current_stream(F.device).cuda_stream), ch.symbol)
-        return tuple(outs)
+        return self._run(self.fn, ch.symbol, inputs, sels, outs, n, F._ld(inputs[0]), device=F.device)
 
 
 def bench_chain(prime: str = "X25519") -> Chain:

@@ -276,7 +276,7 @@ def test_element_major_io_five_inputs(torch_cuda):
               ch.modsqr(ch.modadd_lazy(DA, CB)), ch.modmul(x1, ch.modsqr(ch.modsub_lazy(DA, CB)))):
         ch.output(v)
     f = ch.build()
-    assert "sh[CH * SP]" in ch.source()                           # the shared image
+    assert "#define CHAIN_AOS_IMAGES 1 " in ch.source()               # the shared image (csrc/chain.inc: sh[CHAIN_AOS_IMAGES * CH * SP])
     n = 3 * 512 + 201
     t = [to_dev(_rand(fp, n, 70 + i)) for i in range(5)]
     bit = torch.randint(0, 2, (n,), dtype=torch.int32, device="cuda")
@@ -284,6 +284,45 @@ def test_element_major_io_five_inputs(torch_cuda):
     got = f.aos(*[F.to_aos(x) for x in t], bit)
     for k in range(4):
         assert torch.equal(F.from_aos(got[k]), want[k]), k
+
+
+@pytest.mark.parametrize("P", ["X25519", "X448"])
+def test_shared_entry_body_tail_selector_and_small_tiles(torch_cuda, P):
+    """the one _batch entry body of csrc/chain.inc at 64 bits where the other tests do not reach: a selector on the tail launch (n = 257
+    in rows of an even stride: 128 lanes at two elements, the odd element at its own address with selector entry 256), an unaligned view
+    on the 8-byte path, tiles of 128, and in place over the inputs -- limb for limb the call-by-call sequence of Field"""
+    torch = torch_cuda
+    from modarith_amd.field import Field
+    from modarith_amd.fuse import Chain
+    F, fp = Field(P), derive_any(P)
+    ch = Chain(P, "tailsel")
+    a, b = ch.inputs(2)
+    g, h = ch.modcsw(ch.selector(), a, b)
+    ch.output(ch.modmul(ch.modadd(g, h), ch.modsub(g, h)))
+    ch.output(ch.modmli(h, 121665))
+    f = ch.build()
+
+    def calls(x, y, sel):
+        G, H = x.clone(), y.clone()
+        F.modcsw(sel, G, H)
+        return F.modmul(F.modadd(G, H), F.modsub(G, H)), F.modmli(H, 121665)
+
+    X, Y = to_dev(_rand(fp, 258, 91)), to_dev(_rand(fp, 258, 92))             # rows of 258 words: views of 257 keep an even stride
+    bits = torch.randint(0, 2, (258,), dtype=torch.int32, device="cuda")
+    bits[256] = 1                                                              # the tail's element is swapped: its selector is read
+    for x, y, sel in ((X[:, :257], Y[:, :257], bits[:257].contiguous()),       # aligned, odd n
+                      (X[:, 1:257], Y[:, 1:257], bits[1:257].contiguous())):   # 8 bytes off: one element per lane
+        want = calls(x.contiguous(), y.contiguous(), sel)
+        got = f(x, y, sel)
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), (P, x.shape)
+    x, y, sel = X[:, :256].contiguous(), Y[:, :256].contiguous(), bits[:256].contiguous()
+    want = calls(x, y, sel)
+    got = f(F.to_tiled(x, 128), F.to_tiled(y, 128), sel)
+    assert torch.equal(F.to_flat(got[0]), want[0]) and torch.equal(F.to_flat(got[1]), want[1]), P
+    x, y, sel = X[:, :257], Y[:, :257], bits[:257].contiguous()
+    want = calls(x.contiguous(), y.contiguous(), sel)
+    f(x, y, sel, out=[x, y])                                                   # in place over the inputs (the strided views themselves)
+    assert torch.equal(x, want[0]) and torch.equal(y, want[1]), P
 
 
 def test_empty_and_single_element_batches(torch_cuda):

@@ -30,13 +30,13 @@ def _accept(P, name="accept", **kw):
 def test_w32_source_is_the_call_sequence_on_registers():
     ch = _accept("X25519", wl=32)
     src = ch.source()
-    body = src[src.index("void body("):src.index("template <int EPT>")]
+    body = src[src.index("void body("):src.index("template <int EPT, class IO>")]
     calls = [l.strip() for l in body.splitlines() if l.strip().startswith("F::")]
     assert calls == ["F::modadd(v0, v1, v2);", "F::modsub(v0, v1, v3);", "F::modmul(v2, v3, v4);", "F::modsqr(v4, v5);",
                      "F::modinv(v5, nullptr, v6); inv_normalise<F>(v6);"]
     assert "using namespace ma32;" in src and '#include "kernels32.h"' in src and '#include "w32_X25519.h"' in src
     assert "using P = ma32::P_X25519_W32;" in src and "body<Field<P>>(" in src and "__all" not in src       # one policy, no vote
-    assert "HEAVY = true" in src and "load_soa<P, EPT>(A.in[1], L, t, v1);" in src and "store_soa<P, EPT>(A.out[0], L, t, v6);" in src
+    assert "HEAVY = true" in src and src.count("io.load(1, v1);") == src.count("io.load(1,") == 1 and src.count("io.store(0, v6);") == src.count("io.store(0,") == 1
     assert ch.symbol == "chain_accept_X25519_w32_batch" and ("int %s(" % ch.symbol) in src and "_aos" not in src
     assert ch.traffic_bytes() == 108 and ch.unfused_traffic_bytes() == 468            # 4-byte limbs: two arrays in, one out; five round trips
     assert ch.lib_path().endswith("libmodarith_amd_chain_accept_X25519_w32.so")
