@@ -7,9 +7,11 @@
 //   constexpr int EPT_CAP, CBLOCK;                                        word length 32 only: widest width of the build, workgroup size
 //   #define CHAIN_AOS_IMAGES k                                            word length 64 only: LDS images of the element-major kernel
 //   #define CHAIN_KERNEL_ATTR __attribute__((...))                        optional: an occupancy hint on k_chain
+//   #define CHAIN_NSHARED k                                               optional: batch-wide element operands (ch.shared()), 1 .. 8
 //   template <class F> MA_DEV void body(v0, ..., s0, ...);                the chain on one element's registers
-//   template <int EPT, class IO> MA_DEV void chain_step(IO io);           EPT elements of a lane: io.load(i, v_i) per input, io.sel(k, s_k)
-//                                                                         per selector, the vote, body, io.store(k, v_o) per output
+//   template <int EPT, class IO> MA_DEV void chain_step(IO io);           EPT elements of a lane: io.load(i, v_i) per input, io.shared(j)
+//                                                                         per shared operand, io.sel(k, s_k) per selector, the vote,
+//                                                                         body, io.store(k, v_o) per output
 // and then defines its `extern "C"` symbols over chain_batch() and chain_aos().  Editing this file rebuilds every chain (generate.key_of
 // hashes all of csrc/).
 #if MA_WL == 32
@@ -29,12 +31,33 @@ static_assert(!HEAVY || EPT_CAP == 1, "the long chains run one element per lane"
 #ifndef CHAIN_KERNEL_ATTR
 #define CHAIN_KERNEL_ATTR
 #endif
+// Shared operands (CHAIN_NSHARED > 0): one field element each, the same for every element of the batch.  They travel BY VALUE in the
+// kernel arguments, as the Elem<P> of k_mul_shared (kernels.h) does: wave-uniform, so the compiler may keep them and what it derives
+// from them alone in SGPRs.  The entry points read them from HOST memory before they return (in[NIN .. NIN + CHAIN_NSHARED): Nlimbs words
+// each, as modmuls reads b0_host): no device buffer, no copy to order on the stream, and a call under stream capture bakes the value in.
+// Without them Args, the kernels' signatures and the host bodies are what they were.
+#ifndef CHAIN_NSHARED
+#define CHAIN_NSHARED 0
+#endif
+static_assert(CHAIN_NSHARED >= 0 && CHAIN_NSHARED <= 8, "a chain takes at most 8 shared operands");
+#if CHAIN_NSHARED > 0
+struct Args { const spint* in[NIN]; spint* out[NOUT]; const int* sel[NSEL > 0 ? NSEL : 1]; Elem<P> sh[CHAIN_NSHARED]; };
+MA_DEV const spint* shared_of(const Args& A, int j) { return A.sh[j].l; }
+void shared_from_host(Args& A, const void* const* in) {
+    for (int j = 0; j < CHAIN_NSHARED; j++)
+        for (int i = 0; i < P::N; i++) A.sh[j].l[i] = static_cast<const spint*>(in[NIN + j])[i];
+}
+#else
 struct Args { const spint* in[NIN]; spint* out[NOUT]; const int* sel[NSEL > 0 ? NSEL : 1]; };
+MA_DEV const spint* shared_of(const Args&, int) { return nullptr; }
+void shared_from_host(Args&, const void* const*) {}
+#endif
 
 // ---- limb-interleaved batches: load_soa / store_soa at lane t, EPT consecutive elements
 template <int EPT> struct SoaIO {
     const Args& A; Ld L; size_t t;
     MA_DEV void load(int i, spint (*v)[P::N]) const { load_soa<P, EPT>(A.in[i], L, t, v); }
+    MA_DEV const spint* shared(int j) const { return shared_of(A, j); }
     MA_DEV void sel(int k, int* s) const { static_for<0, EPT>([&](auto E) { s[E] = A.sel[k][(size_t)EPT * t + E]; }); }
     MA_DEV void store(int k, spint (*v)[P::N]) const { store_soa<P, EPT>(A.out[k], L, t, v); }
 };
@@ -43,7 +66,7 @@ __global__ __launch_bounds__(CBLOCK) CHAIN_KERNEL_ATTR void k_chain(Args A, size
     for (size_t t = (size_t)blockIdx.x * CBLOCK + threadIdx.x; t < nthreads; t += (size_t)gridDim.x * CBLOCK) chain_step<EPT>(SoaIO<EPT>{A, L, t});
 }
 
-// in[0 .. NIN): element batches; in[NIN .. NIN + NSEL): int32 selector arrays, one entry per element
+// in[0 .. NIN): element batches; then CHAIN_NSHARED host pointers, one per shared operand; then NSEL int32 selector arrays, one entry per element
 int chain_batch(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) {
     if (n == 0) return 0;
     Ld L(ld);
@@ -55,7 +78,8 @@ int chain_batch(const void* const* in, void* const* out, size_t n, size_t ld, vo
     uintptr_t addr = 0;
     for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; addr |= reinterpret_cast<uintptr_t>(in[i]); }
     for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; addr |= reinterpret_cast<uintptr_t>(out[i]); }
-    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + i];
+    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + CHAIN_NSHARED + i];
+    shared_from_host(A, in);
     hipStream_t s = (hipStream_t)stream;
     const bool tiled = L.s != 63;
     // elements per lane (the rules of the library's pick_ept, capi_field.inc): e elements need n >= e, a stride that is a multiple of e
@@ -72,6 +96,7 @@ int chain_batch(const void* const* in, void* const* out, size_t n, size_t ld, vo
         for (int i = 0; i < NIN; i++) B.in[i] = A.in[i] + o;
         for (int i = 0; i < NOUT; i++) B.out[i] = A.out[i] + o;
         for (int i = 0; i < NSEL; i++) B.sel[i] = A.sel[i] + done;
+        shared_from_host(B, in);                      // (the remainder launch runs on the same shared operands)
         k_chain<1><<<1, CBLOCK, 0, s>>>(B, n - done, Ld(L.ld));
     }
     return check_launch(CHAIN_SYMBOL "_batch");
@@ -149,6 +174,7 @@ struct AosIO {                                        // two elements per lane: 
         if constexpr (CHAIN_AOS_IMAGES == NIN) aos_regs(cnt, sh + i * CH * SP, v);        // (k_chain_aos has filled the images)
         else aos_in(A.in[i] + off, cnt, sh, v);
     }
+    MA_DEV const spint* shared(int j) const { return shared_of(A, j); }       // (straight from the kernel arguments: not through LDS)
     MA_DEV void sel(int k, int* s) const {
         const int t = threadIdx.x;
         const int* d = A.sel[k] + c0;
@@ -169,14 +195,15 @@ __global__ __launch_bounds__(BLOCK) void k_chain_aos(Args A, size_t n) {
     }
 }
 
-// element-major arrays spint x[n][Nlimbs] (16-byte aligned); in[NIN ..): int32 selector arrays as in the _batch form
+// element-major arrays spint x[n][Nlimbs] (16-byte aligned); in[NIN ..): shared operands (host) and int32 selector arrays as in the _batch form
 int chain_aos(const void* const* in, void* const* out, size_t n, void* stream) {
     if (n == 0) return 0;
     Args A;
     bool al = true;
     for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; al = al && aligned16(in[i]); }
     for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; al = al && aligned16(out[i]); }
-    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + i];
+    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + CHAIN_NSHARED + i];
+    shared_from_host(A, in);
     if (!al) { set_error(CHAIN_SYMBOL "_aos: element-major arrays must be 16-byte aligned"); return (int)hipErrorInvalidValue; }
     const size_t chunks = (n + CH - 1) / CH;
     const size_t cap = (size_t)max_blocks_tiled();

@@ -24,7 +24,11 @@ the exact ones.  C-ABI of the built plug-in (modarith_amd/plugins/libmodarith_am
     int chain_<name>_<TAG>_batch(const void *const *in, void *const *out, size_t n, size_t ld, void *stream);
     int chain_<name>_<TAG>_aos(const void *const *in, void *const *out, size_t n, void *stream);     /* element-major x[n][Nlimbs] */
 
-(`in`: the element batches, then one int32 array per selector of modcmv / modcsw.)  Operations: modmul modsqr modadd modsub modneg
+(`in`: the element batches, then one HOST pointer per shared operand, then one int32 array per selector of modcmv / modcsw.)
+`ch.shared()` is an operand that is the same for every element of the batch -- a curve's d, a base point's coordinate, a blinding factor:
+Nlimbs words on the host, read by the entry point before it returns and passed by value in the kernel arguments (wave-uniform: scalar
+registers, no array to stream; a call under stream capture bakes the value in), at most 8 a chain; `ch.modint(k)`, `ch.modone()`, `ch.modzer()`
+are the field's constants as Field<P>::modint / modone / modzer make them.  Operations: modmul modsqr modadd modsub modneg
 modmli nres redc modcpy modinv modpro modsqrt modnsqr modhaf modcmv modcsw and the generic=False forms modadd_lazy modsub_lazy
 modneg_lazy (one level of laziness between reductions, which is how rfc7748.c uses them).
 
@@ -52,10 +56,12 @@ from .plugin import build_plugin
 _NAME_RE = re.compile(r"^[A-Za-z][A-Za-z0-9_]*$")
 # op -> (Field<P> function, operand count, takes an int immediate)
 _OPS = {"modmul": 2, "modadd": 2, "modsub": 2, "modsqr": 1, "modneg": 1, "nres": 1, "redc": 1, "modcpy": 1, "modinv": 1, "modmli": 1,
-        "modadd_lazy": 2, "modsub_lazy": 2, "modneg_lazy": 1, "modnsqr": 1, "modpro": 1, "modsqrt": 1, "modhaf": 1, "modcmv": 2, "modcsw": 2}
+        "modadd_lazy": 2, "modsub_lazy": 2, "modneg_lazy": 1, "modnsqr": 1, "modpro": 1, "modsqrt": 1, "modhaf": 1, "modcmv": 2, "modcsw": 2,
+        "modint": 0, "modone": 0, "modzer": 0}
 _HEAVY = ("modinv", "modpro", "modsqrt")          # long exponentiation chains: one element per lane
 _LAZY = ("modadd_lazy", "modsub_lazy", "modneg_lazy")
 MAX_OPS = 256
+MAX_SHARED = 8                                    # shared operands of a chain: they travel in the kernel arguments (csrc/chain.inc)
 # 32-bit word form: elements per lane and workgroup size of a chain without an inversion.  Measured (tools/w32_chain_rate.py,
 # profiles/w32_chain_rate.json: the four-call chain at 2^24 elements on tiles of 4096, share of the HBM peak over its own bytes): one
 # element per lane in workgroups of 256 runs at 0.770 / 0.770 / 0.763-0.774 for X25519 / NIST256 / X448 against 0.760 / 0.780 / 0.732 at
@@ -93,6 +99,8 @@ class Chain:
         self.params, self.builtin = found[0], found[1] is None      # (generated: params_<TAG>.h / params_<TAG>_w32.h next to its plug-in)
         self.prime, self.name = prime, name
         self.nin = 0
+        self.in_idx: List[int] = []         # the values that are element batches, in the order of in[]
+        self.sh_idx: List[int] = []         # the values that are shared operands (one element for the whole batch), in the order of in[]
         self.nsel = 0                       # per-element int selectors (modcmv / modcsw): int32 arrays after the element inputs
         self.lazy = set()                   # values produced by a generic=False operation
         self.ops: List[tuple] = []          # (op, dst, a, b, imm)
@@ -109,7 +117,23 @@ class Chain:
         if self.ops:
             raise ValueError("declare every input before the first operation")
         self.nin += 1
-        return self._new()
+        v = self._new()
+        self.in_idx.append(v.idx)
+        return v
+
+    def shared(self) -> Val:
+        """an element operand that is the same for every element of the batch: Nlimbs words on the host, passed after the element batches"""
+        if self.ops:
+            raise ValueError("declare every input before the first operation")
+        if len(self.sh_idx) >= MAX_SHARED:
+            raise ValueError("a chain takes at most %d shared operands" % MAX_SHARED)
+        v = self._new()
+        self.sh_idx.append(v.idx)
+        return v
+
+    @property
+    def nshared(self) -> int:
+        return len(self.sh_idx)
 
     def inputs(self, k: int) -> List[Val]:
         return [self.input() for _ in range(k)]
@@ -119,12 +143,12 @@ class Chain:
             if not isinstance(v, Val) or v.chain is not self:
                 raise ValueError("operands must be values of this chain")
 
-    def _op(self, op: str, a: Val, b: Optional[Val] = None, imm: int = 0) -> Val:
-        self._own(a, *([b] if b is not None else []))
+    def _op(self, op: str, a: Optional[Val], b: Optional[Val] = None, imm: int = 0) -> Val:
+        self._own(*[v for v in (a, b) if v is not None])
         if len(self.ops) >= MAX_OPS:
             raise ValueError("chains are limited to %d operations" % MAX_OPS)
         d = self._new()
-        self.ops.append((op, d.idx, a.idx, b.idx if b is not None else -1, int(imm)))
+        self.ops.append((op, d.idx, a.idx if a is not None else -1, b.idx if b is not None else -1, int(imm)))
         return d
 
     def modmul(self, a, b): return self._op("modmul", a, b)
@@ -141,6 +165,15 @@ class Chain:
         if not -(1 << 31) <= int(k) < (1 << 31):
             raise ValueError("modmli takes a C int")
         return self._op("modmli", a, imm=k)
+
+    # the field's constants, as Field<P>::modint / modone / modzer make them (Montgomery form included): no operand
+    def modint(self, k: int):
+        if isinstance(k, bool) or not isinstance(k, int) or not -(1 << 31) <= k < (1 << 31):
+            raise ValueError("modint takes a C int")
+        return self._op("modint", None, imm=k)
+
+    def modone(self): return self._op("modone", None)
+    def modzer(self): return self._op("modzer", None)
 
     # generic=False forms (pseudo.py:294-302, 315-324, 337-346: what rfc7748.c:20 asks for).  Their results carry up to two extra bits;
     # one level of them keeps the limb contract the split products rely on, a lazy sum of lazy sums need not -- refused here
@@ -193,6 +226,8 @@ class Chain:
 
     def output(self, v: Val) -> None:
         self._own(v)
+        if v.idx in self.sh_idx:
+            raise ValueError("a shared operand is not a per-element array: output modcpy() of it")
         self.outs.append(v.idx)
 
     # ------------------------------------------------------------------ emission
@@ -211,7 +246,8 @@ class Chain:
         return "chain_%s_%s_batch" % (self.name, self._tag)
 
     def traffic_bytes(self) -> int:
-        """HBM bytes per element of the fused kernel; the call-by-call sequence moves sum(w N (operands + 1)) instead (w = 8 or 4 bytes a limb)"""
+        """HBM bytes per element of the fused kernel; the call-by-call sequence moves sum(w N (operands + 1)) instead (w = 8 or 4 bytes a limb).
+        A shared operand costs the fused kernel nothing (it is in the kernel arguments); call by call it is an array like any other operand"""
         return (self.wl // 8) * self.params.nlimbs * (self.nin + len(self.outs)) + 4 * self.nsel
 
     def unfused_traffic_bytes(self) -> int:
@@ -236,6 +272,10 @@ class Chain:
                 L.append("    F::modinv(v%d, nullptr, v%d); inv_normalise<F>(v%d);" % (a, d, d))
             elif op == "modmli":
                 L.append("    F::modmli(v%d, %d, v%d);" % (a, imm, d))
+            elif op == "modint":
+                L.append("    F::modint(%d, v%d);" % (imm, d))
+            elif _OPS[op] == 0:
+                L.append("    F::%s(v%d);" % (op, d))
             elif _OPS[op] == 2:
                 L.append("    F::%s(v%d, v%d, v%d);" % (op, a, b, d))
             else:
@@ -250,6 +290,7 @@ class Chain:
         if not self.nin or not self.outs:
             raise ValueError("a chain needs at least one input and one output")
         P, nv, N, w32 = self.prime, self.nvals, self.params.nlimbs, self.wl == 32
+        shared = set(self.sh_idx)                         # one element for the whole batch: a pointer into the kernel arguments, not a per-lane array
         if w32:
             if policy != "vote":
                 raise ValueError("word length 32 has one product policy: there is nothing to force")
@@ -276,16 +317,21 @@ class Chain:
             head = ['#include "params_%s.h"' % P, '#include "modarith_amd.h"', '#include "capi_common.h"', '#include "kernels.h"', "#include <utility>", "",
                     "namespace {", "using namespace ma;", "using P = ma::P_%s;" % P]
             shape = ["#define CHAIN_AOS_IMAGES %d   // LDS images of the element-major kernel: one per input array, 1 = one shared image, 0 = no kernel (more than 14 limbs)" % images]
+        if shared:
+            shape.append("#define CHAIN_NSHARED %d   // operands that are one element for the whole batch: host pointers after the element batches in in[], by value in the kernel arguments" % self.nshared)
         if waves:
             shape.append("#define CHAIN_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(%d, %d)))" % (waves, waves))
-        args = ", ".join(["v%d[E]" % i for i in range(nv)] + ["s%d[E]" % k for k in range(self.nsel)])
+        args = ", ".join([("v%d" if i in shared else "v%d[E]") % i for i in range(nv)] + ["s%d[E]" % k for k in range(self.nsel)])
+        # modint of a negative int is the word (spint)k, outside the limb contract at 64 bits: such a chain runs the exact products, as Field.modint does
+        if policy == "vote" and any(o[0] == "modint" and o[4] < 0 for o in self.ops):
+            policy = "exact"
         if w32:
             run = ["    static_for<0, EPT>([&](auto E) { body<Field<P>>(%s); });" % args]
         else:
             run = ["    bool fast = %s;" % ("true" if policy == "fast" else "false"),
                    "    if constexpr (P::SPLIT > 0 && %s) {" % ("true" if policy == "vote" else "false"),
-                   "        bool ok = true;",
-                   "        static_for<0, EPT>([&](auto E) { ok = ok && " + " && ".join("in_split_contract<P>(v%d[E])" % i for i in range(self.nin)) + "; });",
+                   "        bool ok = %s;" % (" && ".join("in_split_contract<P>(v%d)" % i for i in self.sh_idx) or "true"),
+                   "        static_for<0, EPT>([&](auto E) { ok = ok && " + " && ".join("in_split_contract<P>(v%d[E])" % i for i in self.in_idx) + "; });",
                    "        fast = __all(ok);",
                    "    }",
                    "    if (fast) {",
@@ -293,19 +339,20 @@ class Chain:
                    "    } else {",
                    "        static_for<0, EPT>([&](auto E) { body<Field<P, false>>(%s); });" % args,
                    "    }"]
-        L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s%s: %d inputs, %d operations, %d outputs; kernels and entry bodies: csrc/chain.inc"
-             % (self.name, P, ", 32-bit word form" if w32 else "", self.nin, len(self.ops), len(self.outs))]
+        L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s%s: %d inputs%s, %d operations, %d outputs; kernels and entry bodies: csrc/chain.inc"
+             % (self.name, P, ", 32-bit word form" if w32 else "", self.nin, ", %d shared" % self.nshared if shared else "", len(self.ops), len(self.outs))]
         L += head + ['#define CHAIN_SYMBOL "%s"   // the entry points: <this>_batch%s' % (self.symbol[:-6], "" if w32 else ", <this>_aos"),
                      "constexpr int NIN = %d, NOUT = %d, NSEL = %d;" % (self.nin, len(self.outs), self.nsel),
                      "constexpr bool HEAVY = %s;   // one element per lane on every batch: an inversion, a progenitor or a square root in the chain%s"
                      % ("true" if heavy else "false", "" if w32 else ", or build(ept=1)")] + shape
         L += ["", "// the chain on one element's registers; F = %s" % ("Field<P> (one product policy at this word length: no vote)" if w32 else "Field<P, FAST>"),
-              "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i < self.nin else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)])]
+              "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i < self.nin + self.nshared else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)])]
         L += self._body_lines()
         L += ["}", "", "// EPT elements of a lane through the chain; io is how the calling kernel of csrc/chain.inc reaches them in memory",
               "template <int EPT, class IO> MA_DEV void chain_step(IO io) {",
-              "    " + " ".join("spint v%d[EPT][P::N];" % i for i in range(nv))]
-        L += ["    io.load(%d, v%d);" % (i, i) for i in range(self.nin)]
+              "    " + " ".join("spint v%d[EPT][P::N];" % i for i in range(nv) if i not in shared)]
+        L += ["    io.load(%d, v%d);" % (k, i) for k, i in enumerate(self.in_idx)]
+        L += ["    const spint* v%d = io.shared(%d);" % (i, k) for k, i in enumerate(self.sh_idx)]
         L += ["    int s%d[EPT]; io.sel(%d, s%d);" % (k, k, k) for k in range(self.nsel)]
         L += run
         L += ["    io.store(%d, v%d);" % (k, o) for k, o in enumerate(self.outs)]
@@ -335,15 +382,16 @@ class Chain:
         src, obj, meta = (os.path.join(d, base + e) for e in (".hip", ".o", ".json"))
         lib = self.lib_path(d)
         emit._write(src, src_text)
-        record = {"chain": self.name, "prime": self.prime, "wl": self.wl, "inputs": self.nin, "selectors": self.nsel, "outputs": len(self.outs),
-                  "ops": [o[0] for o in self.ops], "symbol": self.symbol}
+        record = {"chain": self.name, "prime": self.prime, "wl": self.wl, "inputs": self.nin, "shared": self.nshared, "selectors": self.nsel,
+                  "outputs": len(self.outs), "ops": [o[0] for o in self.ops], "symbol": self.symbol}
         built = build_plugin(d, lib, meta, record, _gen.key_of(src_text, emit.header_text(self.params)), [(src, obj, [])], "chain", force, verbose)
         return FusedChain(self, lib, built)
 
 
 class FusedChain:
     """a built chain: call it with one device batch per input (flat [N, n] or tiled [n / tile, N, tile], all the same shape; int64
-    limbs, or int32 for a chain of the 32-bit word form)"""
+    limbs, or int32 for a chain of the 32-bit word form), then one host element per shared operand (Nlimbs ints or a CPU integer
+    tensor, as Field.modmuls takes b0), then one int32 device array per selector"""
     def __init__(self, chain: Chain, lib: str, built: bool):
         self.chain, self.path, self.built = chain, lib, built
         _lib.load()
@@ -355,18 +403,34 @@ class FusedChain:
 
     def _split(self, inputs, what: str):
         ch = self.chain
-        if len(inputs) != ch.nin + ch.nsel:
-            raise ValueError("chain %s takes %d element %s followed by %d int32 selector arrays" % (ch.name, ch.nin, what, ch.nsel))
-        return inputs[:ch.nin], inputs[ch.nin:]
+        if len(inputs) != ch.nin + ch.nshared + ch.nsel:
+            raise ValueError("chain %s takes %d element %s followed by %d shared operands (%d limbs each, on the host) and %d int32 selector arrays"
+                             % (ch.name, ch.nin, what, ch.nshared, ch.params.nlimbs, ch.nsel))
+        return inputs[:ch.nin], [self._limbs(b) for b in inputs[ch.nin:ch.nin + ch.nshared]], inputs[ch.nin + ch.nshared:]
 
-    def _run(self, fn, symbol: str, elems, sels, outs, n: int, *ld, device=None):
-        """what both entries share: the selector check, the pointer arrays and the call on the current stream of the batches' device"""
+    def _limbs(self, b):
+        """one shared operand as host words of the chain's word length: a sequence of Nlimbs ints or a CPU integer tensor, as Field.modmuls takes b0"""
+        ch = self.chain
+        if hasattr(b, "is_cuda"):
+            if b.is_cuda or b.is_floating_point() or b.dim() != 1:
+                raise ValueError("a shared operand is %d limbs on the host: a sequence of ints or a CPU integer tensor" % ch.params.nlimbs)
+            b = b.tolist()
+        b = [int(v) for v in b]
+        if len(b) != ch.params.nlimbs:
+            raise ValueError("a shared operand is %d limbs on the host (got %d)" % (ch.params.nlimbs, len(b)))
+        word = ctypes.c_uint64 if ch.wl == 64 else ctypes.c_uint32
+        return (word * len(b))(*[v & ((1 << ch.wl) - 1) for v in b])          # (signed tensors hold the same words)
+
+    def _run(self, fn, symbol: str, elems, shared, sels, outs, n: int, *ld, device=None):
+        """what both entries share: the selector check, the pointer arrays and the call on the current stream of the batches' device.
+        The entry point reads the shared operands' limbs before it returns: the host arrays need to live no longer than this call"""
         import torch
         for d in sels:
             if d.dtype != torch.int32 or d.numel() != n or not d.is_cuda or not d.is_contiguous() or (device is not None and d.device != device):
                 raise ValueError("selectors are contiguous int32 device tensors with one 0/1 entry per element")
         dev = device if device is not None else elems[0].device
-        ins = (ctypes.c_void_p * (len(elems) + len(sels)))(*[t.data_ptr() for t in list(elems) + list(sels)])
+        ptrs = [t.data_ptr() for t in elems] + [ctypes.addressof(b) for b in shared] + [t.data_ptr() for t in sels]
+        ins = (ctypes.c_void_p * len(ptrs))(*ptrs)
         ous = (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
         with torch.cuda.device(dev):
             _lib.check(fn(ins, ous, n, *ld, torch.cuda.current_stream(dev).cuda_stream), symbol)
@@ -374,13 +438,13 @@ class FusedChain:
 
     def aos(self, *inputs, out: Optional[Sequence] = None):
         """the same chain over element-major device arrays int64 [n, Nlimbs] (`spint x[n][Nlimbs]`, how CPU callers of field.c hold
-        elements): no aos_to_soa / soa_to_aos passes around it; selectors follow the element arrays as in __call__"""
+        elements): no aos_to_soa / soa_to_aos passes around it; shared operands and selectors follow the element arrays as in __call__"""
         import torch
         ch = self.chain
         N = ch.params.nlimbs
         if ch.wl == 32:
             raise ValueError("the element-major entry is not built at word length 32: convert with modarith_amd_w32_aos_to_soa and call %s" % ch.symbol)
-        elems, sels = self._split(inputs, "arrays")
+        elems, shared, sels = self._split(inputs, "arrays")
         n = elems[0].shape[0]
         outs = list(out) if out is not None else [torch.empty_like(elems[0]) for _ in ch.outs]
         for t in list(elems) + outs:
@@ -389,12 +453,12 @@ class FusedChain:
         fn = getattr(self.lib, ch.aos_symbol)
         fn.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_void_p]
         fn.restype = ctypes.c_int
-        return self._run(fn, ch.aos_symbol, elems, sels, outs, n)
+        return self._run(fn, ch.aos_symbol, elems, shared, sels, outs, n)
 
     def __call__(self, *inputs, out: Optional[Sequence] = None, device=None):
         from .field import Field
         ch = self.chain
-        inputs, sels = self._split(inputs, "batches")
+        inputs, shared, sels = self._split(inputs, "batches")
         dev = device if device is not None else inputs[0].device
         F = self._fields.get(dev)
         if F is None:                                  # binding a Field derives the prime's constants: once per device, not per call
@@ -403,7 +467,7 @@ class FusedChain:
         if len(outs) != len(ch.outs):
             raise ValueError("chain %s has %d outputs" % (ch.name, len(ch.outs)))
         n = F._chk(*inputs, *outs)
-        return self._run(self.fn, ch.symbol, inputs, sels, outs, n, F._ld(inputs[0]), device=F.device)
+        return self._run(self.fn, ch.symbol, inputs, shared, sels, outs, n, F._ld(inputs[0]), device=F.device)
 
 
 def bench_chain(prime: str = "X25519") -> Chain:
@@ -419,9 +483,10 @@ def bench_chain(prime: str = "X25519") -> Chain:
 #   python -m modarith_amd.fuse 32 X25519 accept "..."        (the same chain over the 32-bit word form)
 #   python -m modarith_amd.fuse X25519 accept "in x, y; t = modadd(x, y); w = modsub(x, y); s = modsqr(modmul(t, w)); out modinv(s)"
 def parse(prime: str, name: str, text: str, wl: int = 64) -> Chain:
-    """statements separated by ';':  `in a, b`  (element inputs, in order) | `sel d` (int32 selector inputs) | `v = f(args)` |
+    """statements separated by ';':  `in a, b`  (element inputs, in order) | `shared b, d` (operands that are one element for the whole
+    batch) | `sel d` (int32 selector inputs) | `v = f(args)` |
     `g2, f2 = modcsw(d, g, f)` | `out expr, ...`.  Expressions nest: modsqr(modmul(a, b)).  Integers are accepted where the
-    function takes one (modmli, modnsqr).  Function names are the chain's methods, i.e. field.c's."""
+    function takes one (modmli, modnsqr, modint); modone() and modzer() take nothing.  Function names are the chain's methods, i.e. field.c's."""
     import ast
     ch = Chain(prime, name, wl)
     env = {}
@@ -447,6 +512,9 @@ def parse(prime: str, name: str, text: str, wl: int = 64) -> Chain:
         if head == "in":
             for nm in [t.strip() for t in rest.split(",")]:
                 env[nm] = ch.input()
+        elif head == "shared":
+            for nm in [t.strip() for t in rest.split(",")]:
+                env[nm] = ch.shared()
         elif head == "sel":
             for nm in [t.strip() for t in rest.split(",")]:
                 env[nm] = ch.selector()
@@ -487,8 +555,9 @@ def main(argv: List[str]) -> int:
         print(e)
         return 2
     print("%s %s" % ("built" if f.built else "up to date:", f.path))
-    print("int %s(const void *const *in /* %d element batches%s */, void *const *out /* %d */, size_t n, size_t ld, void *stream);"
-          % (ch.symbol, ch.nin, (", then %d int32 selector arrays" % ch.nsel) if ch.nsel else "", len(ch.outs)))
+    print("int %s(const void *const *in /* %d element batches%s%s */, void *const *out /* %d */, size_t n, size_t ld, void *stream);"
+          % (ch.symbol, ch.nin, (", then %d host pointers to shared operands of %d limbs" % (ch.nshared, ch.params.nlimbs)) if ch.nshared else "",
+             (", then %d int32 selector arrays" % ch.nsel) if ch.nsel else "", len(ch.outs)))
     if ch.wl == 64:
         print("int %s(const void *const *in, void *const *out, size_t n, void *stream);   /* the same over element-major arrays x[n][Nlimbs] */" % ch.aos_symbol)
     print("HBM bytes per element: %d fused, %d call by call" % (ch.traffic_bytes(), ch.unfused_traffic_bytes()))
