@@ -8,10 +8,11 @@
 //   #define CHAIN_AOS_IMAGES k                                            word length 64 only: LDS images of the element-major kernel
 //   #define CHAIN_KERNEL_ATTR __attribute__((...))                        optional: an occupancy hint on k_chain
 //   #define CHAIN_NSHARED k                                               optional: batch-wide element operands (ch.shared()), 1 .. 8
+//   #define CHAIN_NPRED k                                                 optional: int32 results (ch.output() of a Pred), one entry per element
 //   template <class F> MA_DEV void body(v0, ..., s0, ...);                the chain on one element's registers
 //   template <int EPT, class IO> MA_DEV void chain_step(IO io);           EPT elements of a lane: io.load(i, v_i) per input, io.shared(j)
 //                                                                         per shared operand, io.sel(k, s_k) per selector, the vote,
-//                                                                         body, io.store(k, v_o) per output
+//                                                                         body, io.store(k, v_o) per output, io.pred(k, s_j) per int output
 // and then defines its `extern "C"` symbols over chain_batch() and chain_aos().  Editing this file rebuilds every chain (generate.key_of
 // hashes all of csrc/).
 #if MA_WL == 32
@@ -40,15 +41,28 @@ static_assert(!HEAVY || EPT_CAP == 1, "the long chains run one element per lane"
 #define CHAIN_NSHARED 0
 #endif
 static_assert(CHAIN_NSHARED >= 0 && CHAIN_NSHARED <= 8, "a chain takes at most 8 shared operands");
+// Int results (CHAIN_NPRED > 0): the ints a chain computes (modis0 / modis1 / modsign / modcmp / modqr and the 0/1 expressions on them) that
+// it declares outputs.  One int32 device array of n contiguous entries each, out[NOUT .. NOUT + CHAIN_NPRED), indexed BY ELEMENT as the
+// selectors are, whatever the layout of the element batches.  A chain may have nothing else to return (NOUT == 0).  An int result may be
+// the array of a selector input: a lane reads its entries (io.sel) before it stores them (io.pred), and no other lane touches them.
+#ifndef CHAIN_NPRED
+#define CHAIN_NPRED 0
+#endif
+static_assert(CHAIN_NPRED >= 0 && NOUT + CHAIN_NPRED > 0, "a chain returns at least one array");
+#if CHAIN_NPRED > 0
+#define CHAIN_PRED_ARGS int* pred[CHAIN_NPRED];
+#else
+#define CHAIN_PRED_ARGS
+#endif
 #if CHAIN_NSHARED > 0
-struct Args { const spint* in[NIN]; spint* out[NOUT]; const int* sel[NSEL > 0 ? NSEL : 1]; Elem<P> sh[CHAIN_NSHARED]; };
+struct Args { const spint* in[NIN]; spint* out[NOUT > 0 ? NOUT : 1]; const int* sel[NSEL > 0 ? NSEL : 1]; CHAIN_PRED_ARGS Elem<P> sh[CHAIN_NSHARED]; };
 MA_DEV const spint* shared_of(const Args& A, int j) { return A.sh[j].l; }
 void shared_from_host(Args& A, const void* const* in) {
     for (int j = 0; j < CHAIN_NSHARED; j++)
         for (int i = 0; i < P::N; i++) A.sh[j].l[i] = static_cast<const spint*>(in[NIN + j])[i];
 }
 #else
-struct Args { const spint* in[NIN]; spint* out[NOUT]; const int* sel[NSEL > 0 ? NSEL : 1]; };
+struct Args { const spint* in[NIN]; spint* out[NOUT > 0 ? NOUT : 1]; const int* sel[NSEL > 0 ? NSEL : 1]; CHAIN_PRED_ARGS };
 MA_DEV const spint* shared_of(const Args&, int) { return nullptr; }
 void shared_from_host(Args&, const void* const*) {}
 #endif
@@ -60,6 +74,9 @@ template <int EPT> struct SoaIO {
     MA_DEV const spint* shared(int j) const { return shared_of(A, j); }
     MA_DEV void sel(int k, int* s) const { static_for<0, EPT>([&](auto E) { s[E] = A.sel[k][(size_t)EPT * t + E]; }); }
     MA_DEV void store(int k, spint (*v)[P::N]) const { store_soa<P, EPT>(A.out[k], L, t, v); }
+#if CHAIN_NPRED > 0
+    MA_DEV void pred(int k, const int* s) const { static_for<0, EPT>([&](auto E) { A.pred[k][(size_t)EPT * t + E] = s[E]; }); }   // (one 4-byte store per element: no alignment asked of the array)
+#endif
 };
 template <int EPT>
 __global__ __launch_bounds__(CBLOCK) CHAIN_KERNEL_ATTR void k_chain(Args A, size_t nthreads, Ld L) {
@@ -67,6 +84,7 @@ __global__ __launch_bounds__(CBLOCK) CHAIN_KERNEL_ATTR void k_chain(Args A, size
 }
 
 // in[0 .. NIN): element batches; then CHAIN_NSHARED host pointers, one per shared operand; then NSEL int32 selector arrays, one entry per element
+// out[0 .. NOUT): element batches; then CHAIN_NPRED int32 arrays of n entries
 int chain_batch(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) {
     if (n == 0) return 0;
     Ld L(ld);
@@ -79,6 +97,9 @@ int chain_batch(const void* const* in, void* const* out, size_t n, size_t ld, vo
     for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; addr |= reinterpret_cast<uintptr_t>(in[i]); }
     for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; addr |= reinterpret_cast<uintptr_t>(out[i]); }
     for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + CHAIN_NSHARED + i];
+#if CHAIN_NPRED > 0
+    for (int i = 0; i < CHAIN_NPRED; i++) A.pred[i] = (int*)out[NOUT + i];
+#endif
     shared_from_host(A, in);
     hipStream_t s = (hipStream_t)stream;
     const bool tiled = L.s != 63;
@@ -96,6 +117,9 @@ int chain_batch(const void* const* in, void* const* out, size_t n, size_t ld, vo
         for (int i = 0; i < NIN; i++) B.in[i] = A.in[i] + o;
         for (int i = 0; i < NOUT; i++) B.out[i] = A.out[i] + o;
         for (int i = 0; i < NSEL; i++) B.sel[i] = A.sel[i] + done;
+#if CHAIN_NPRED > 0
+        for (int i = 0; i < CHAIN_NPRED; i++) B.pred[i] = A.pred[i] + done;
+#endif
         shared_from_host(B, in);                      // (the remainder launch runs on the same shared operands)
         k_chain<1><<<1, CBLOCK, 0, s>>>(B, n - done, Ld(L.ld));
     }
@@ -181,6 +205,13 @@ struct AosIO {                                        // two elements per lane: 
         static_for<0, 2>([&](auto E) { s[E] = (2 * (size_t)t + E < cnt) ? d[2 * (size_t)t + E] : 0; });
     }
     MA_DEV void store(int k, spint (*v)[P::N]) const { aos_out(A.out[k] + off, cnt, sh, v); }
+#if CHAIN_NPRED > 0
+    MA_DEV void pred(int k, const int* s) const {
+        const int t = threadIdx.x;
+        int* d = A.pred[k] + c0;
+        static_for<0, 2>([&](auto E) { if (2 * (size_t)t + E < cnt) d[2 * (size_t)t + E] = s[E]; });
+    }
+#endif
 };
 __global__ __launch_bounds__(BLOCK) void k_chain_aos(Args A, size_t n) {
     __shared__ spint sh[CHAIN_AOS_IMAGES * CH * SP];
@@ -195,7 +226,8 @@ __global__ __launch_bounds__(BLOCK) void k_chain_aos(Args A, size_t n) {
     }
 }
 
-// element-major arrays spint x[n][Nlimbs] (16-byte aligned); in[NIN ..): shared operands (host) and int32 selector arrays as in the _batch form
+// element-major arrays spint x[n][Nlimbs] (16-byte aligned); in[NIN ..): shared operands (host) and int32 selector arrays as in the _batch form;
+// out[NOUT ..): the int32 results, n entries each (no alignment asked of them)
 int chain_aos(const void* const* in, void* const* out, size_t n, void* stream) {
     if (n == 0) return 0;
     Args A;
@@ -203,6 +235,9 @@ int chain_aos(const void* const* in, void* const* out, size_t n, void* stream) {
     for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; al = al && aligned16(in[i]); }
     for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; al = al && aligned16(out[i]); }
     for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + CHAIN_NSHARED + i];
+#if CHAIN_NPRED > 0
+    for (int i = 0; i < CHAIN_NPRED; i++) A.pred[i] = (int*)out[NOUT + i];
+#endif
     shared_from_host(A, in);
     if (!al) { set_error(CHAIN_SYMBOL "_aos: element-major arrays must be 16-byte aligned"); return (int)hipErrorInvalidValue; }
     const size_t chunks = (n + CH - 1) / CH;

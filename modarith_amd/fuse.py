@@ -24,13 +24,24 @@ the exact ones.  C-ABI of the built plug-in (modarith_amd/plugins/libmodarith_am
     int chain_<name>_<TAG>_batch(const void *const *in, void *const *out, size_t n, size_t ld, void *stream);
     int chain_<name>_<TAG>_aos(const void *const *in, void *const *out, size_t n, void *stream);     /* element-major x[n][Nlimbs] */
 
-(`in`: the element batches, then one HOST pointer per shared operand, then one int32 array per selector of modcmv / modcsw.)
+(`in`: the element batches, then one HOST pointer per shared operand, then one int32 array per selector of modcmv / modcsw;
+`out`: the element batches, then one int32 array per int output.)
 `ch.shared()` is an operand that is the same for every element of the batch -- a curve's d, a base point's coordinate, a blinding factor:
 Nlimbs words on the host, read by the entry point before it returns and passed by value in the kernel arguments (wave-uniform: scalar
 registers, no array to stream; a call under stream capture bakes the value in), at most 8 a chain; `ch.modint(k)`, `ch.modone()`, `ch.modzer()`
 are the field's constants as Field<P>::modint / modone / modzer make them.  Operations: modmul modsqr modadd modsub modneg
 modmli nres redc modcpy modinv modpro modsqrt modnsqr modhaf modcmv modcsw and the generic=False forms modadd_lazy modsub_lazy
 modneg_lazy (one level of laziness between reductions, which is how rfc7748.c uses them).
+
+A chain can decide (edwards.c:271, 313-325): `ch.modis0(a)`, `ch.modis1(a)`, `ch.modsign(a)`, `ch.modcmp(a, b)`, `ch.modqr(x, h=None)` are
+Field<P>'s functions of those names and return a `Pred`, an int computed inside the chain; `ch.lnot(d)`, `ch.land(d, e)`, `ch.lor(d, e)`,
+`ch.lxor(d, e)` are the reference's own `1 - d`, `d & e`, `d | e`, `d ^ e` on predicates and selectors -- defined for operands that are 0 or 1,
+as they are there; `modcmv` / `modcsw` take a `Pred` where they take a selector (still lane predication: no branch, no `?:`, no loop on a
+computed int); `ch.modsqrt(a, h)`, `ch.modinv(a, h)`, `ch.modqr(x, h)` pass the progenitor `h = ch.modpro(a)` where they pass NULL otherwise;
+and `ch.output(p)` of a `Pred` is an int32 result of one entry per element.  `out` of both entries is then the element arrays followed by
+the int32 arrays (n contiguous entries each, indexed by element for flat and tiled batches alike, no alignment asked; one may be the array
+of a selector input: a lane reads its entries before it stores), and a chain may have no other output: `oncurve_chain()` below reads two
+coordinate arrays and writes 4 bytes per element, `decompress_chain()` is edwards.c:290-334 as one kernel.
 
 Word length 32: `Chain(prime, name, wl=32)` is the same chain over the 32-bit word form of X25519, NIST256 and X448 (csrc/kernels32.h,
 namespace ma32; int32 batches of `Field(prime, wl=32)`): what a port of the reference's per-thread CUDA form (simd/pseudo_cuda.py 32)
@@ -57,8 +68,12 @@ _NAME_RE = re.compile(r"^[A-Za-z][A-Za-z0-9_]*$")
 # op -> (Field<P> function, operand count, takes an int immediate)
 _OPS = {"modmul": 2, "modadd": 2, "modsub": 2, "modsqr": 1, "modneg": 1, "nres": 1, "redc": 1, "modcpy": 1, "modinv": 1, "modmli": 1,
         "modadd_lazy": 2, "modsub_lazy": 2, "modneg_lazy": 1, "modnsqr": 1, "modpro": 1, "modsqrt": 1, "modhaf": 1, "modcmv": 2, "modcsw": 2,
-        "modint": 0, "modone": 0, "modzer": 0}
-_HEAVY = ("modinv", "modpro", "modsqrt")          # long exponentiation chains: one element per lane
+        "modint": 0, "modone": 0, "modzer": 0,
+        "modis0": 1, "modis1": 1, "modsign": 1, "modcmp": 2, "modqr": 1, "lnot": 0, "land": 0, "lor": 0, "lxor": 0}
+_HEAVY = ("modinv", "modpro", "modsqrt", "modqr")  # long exponentiation chains: one element per lane
+_PREDS = ("modis0", "modis1", "modsign", "modcmp", "modqr")      # Field<P> functions that return an int: the result is a Pred
+_INT_OPS = {"lnot": "1 - s%d", "land": "s%d & s%d", "lor": "s%d | s%d", "lxor": "s%d ^ s%d"}     # the plain C the reference writes on its 0/1 ints
+_WITH_H = ("modinv", "modsqrt", "modqr")          # take an optional progenitor h = modpro(a)
 _LAZY = ("modadd_lazy", "modsub_lazy", "modneg_lazy")
 MAX_OPS = 256
 MAX_SHARED = 8                                    # shared operands of a chain: they travel in the kernel arguments (csrc/chain.inc)
@@ -79,6 +94,14 @@ class Val:
 
 class Sel:
     """a per-element int selector input of a chain"""
+    def __init__(self, chain: "Chain", idx: int):
+        self.chain, self.idx = chain, idx
+
+
+class Pred:
+    """an int-valued intermediate of a chain (0 / 1), computed inside it: the result of modis0 / modis1 / modsign / modcmp / modqr or of
+    lnot / land / lor / lxor.  A selector of modcmv / modcsw, an operand of the int expressions, an int32 output.  Ints share one index
+    space (s<k> in the emitted text): the selector inputs first, then the computed ones"""
     def __init__(self, chain: "Chain", idx: int):
         self.chain, self.idx = chain, idx
 
@@ -105,6 +128,8 @@ class Chain:
         self.lazy = set()                   # values produced by a generic=False operation
         self.ops: List[tuple] = []          # (op, dst, a, b, imm)
         self.outs: List[int] = []
+        self.npred = 0                      # ints computed inside the chain (Pred): s<nsel> .. s<nsel + npred - 1>
+        self.pouts: List[int] = []          # the ints that are outputs (indices of the int space), in the order of out[] after the element outputs
         self.nvals = 0
 
     # ------------------------------------------------------------------ building
@@ -140,6 +165,8 @@ class Chain:
 
     def _own(self, *vs: Val):
         for v in vs:
+            if isinstance(v, (Pred, Sel)):
+                raise ValueError("an int value (a predicate or a selector) is not an element operand")
             if not isinstance(v, Val) or v.chain is not self:
                 raise ValueError("operands must be values of this chain")
 
@@ -159,7 +186,7 @@ class Chain:
     def nres(self, a): return self._op("nres", a)
     def redc(self, a): return self._op("redc", a)
     def modcpy(self, a): return self._op("modcpy", a)
-    def modinv(self, a): return self._op("modinv", a)
+    def modinv(self, a, h=None): return self._op("modinv", a, h)      # h: the progenitor modpro(a) where the caller has it (field.c passes NULL otherwise)
 
     def modmli(self, a, k: int):
         if not -(1 << 31) <= int(k) < (1 << 31):
@@ -192,7 +219,7 @@ class Chain:
     def modsub_lazy(self, a, b): return self._lazy("modsub_lazy", a, b)
     def modneg_lazy(self, a): return self._lazy("modneg_lazy", a)
     def modpro(self, a): return self._op("modpro", a)
-    def modsqrt(self, a): return self._op("modsqrt", a)
+    def modsqrt(self, a, h=None): return self._op("modsqrt", a, h)
     def modhaf(self, a): return self._op("modhaf", a)
 
     def modnsqr(self, a, k: int):
@@ -208,9 +235,43 @@ class Chain:
         return Sel(self, self.nsel - 1)
 
     def _sel(self, d):
-        if not isinstance(d, Sel) or d.chain is not self:
-            raise ValueError("the selector must come from this chain's selector()")
-        return d.idx
+        if not isinstance(d, (Sel, Pred)) or d.chain is not self:
+            raise ValueError("the selector must come from this chain's selector() or be an int computed in this chain")
+        return d.idx if isinstance(d, Sel) else self.nsel + d.idx
+
+    # ints computed inside the chain.  A Pred's place in the int space is nsel + its own count: selectors are declared before the first operation
+    def _pred(self, op: str, a: int = -1, b: int = -1) -> Pred:
+        if len(self.ops) >= MAX_OPS:
+            raise ValueError("chains are limited to %d operations" % MAX_OPS)
+        d = Pred(self, self.npred)
+        self.npred += 1
+        self.ops.append((op, self.nsel + d.idx, a, b, 0))
+        return d
+
+    def _test(self, op: str, a: Val, b: Optional[Val] = None) -> Pred:
+        self._own(*[v for v in (a, b) if v is not None])
+        return self._pred(op, a.idx, b.idx if b is not None else -1)
+
+    def modis0(self, a): return self._test("modis0", a)
+    def modis1(self, a): return self._test("modis1", a)
+    def modsign(self, a): return self._test("modsign", a)
+    def modcmp(self, a, b): return self._test("modcmp", a, b)
+
+    def modqr(self, x, h=None):
+        """1 where x is a quadratic residue or zero (field.c's modqr(h, x)); h: the progenitor modpro(x) where the caller has it"""
+        return self._test("modqr", x, h)
+
+    # the reference's own expressions on such ints (`1 - d`, `d & e`, ...): defined for operands that are 0 or 1, as they are there
+    def _ints(self, *ds):
+        for d in ds:
+            if not isinstance(d, (Sel, Pred)):
+                raise ValueError("int expressions take predicates and selectors, not element values")
+        return [self._sel(d) for d in ds]
+
+    def lnot(self, d): return self._pred("lnot", *self._ints(d))
+    def land(self, d, e): return self._pred("land", *self._ints(d, e))
+    def lor(self, d, e): return self._pred("lor", *self._ints(d, e))
+    def lxor(self, d, e): return self._pred("lxor", *self._ints(d, e))
 
     def modcmv(self, d, g, f):
         """f' = d ? g : f  (constant time: lane-predicated selects, pseudo.py:1017-1048)"""
@@ -224,7 +285,15 @@ class Chain:
         self.ops.append(("modcsw", g2.idx, g.idx, f.idx, k, f2.idx))
         return g2, f2
 
-    def output(self, v: Val) -> None:
+    def output(self, v) -> None:
+        """an element value: a limb array like the inputs; a Pred: an int32 array of one entry per element, after the element outputs in out[]"""
+        if isinstance(v, Sel):
+            raise ValueError("a selector is the caller's own array: there is nothing to output")
+        if isinstance(v, Pred):
+            if v.chain is not self:
+                raise ValueError("operands must be values of this chain")
+            self.pouts.append(self.nsel + v.idx)
+            return
         self._own(v)
         if v.idx in self.sh_idx:
             raise ValueError("a shared operand is not a per-element array: output modcpy() of it")
@@ -248,16 +317,45 @@ class Chain:
     def traffic_bytes(self) -> int:
         """HBM bytes per element of the fused kernel; the call-by-call sequence moves sum(w N (operands + 1)) instead (w = 8 or 4 bytes a limb).
         A shared operand costs the fused kernel nothing (it is in the kernel arguments); call by call it is an array like any other operand"""
-        return (self.wl // 8) * self.params.nlimbs * (self.nin + len(self.outs)) + 4 * self.nsel
+        return (self.wl // 8) * self.params.nlimbs * (self.nin + len(self.outs)) + 4 * self.nsel + 4 * len(self.pouts)
 
     def unfused_traffic_bytes(self) -> int:
-        return sum((self.wl // 8) * self.params.nlimbs * (_OPS[o[0]] + (2 if o[0] == "modcsw" else 1)) + (4 if o[0] in ("modcmv", "modcsw") else 0) for o in self.ops)
+        """a predicate call reads its operand arrays and writes 4 bytes; a selector, streamed in or computed, is a 4-byte read of the call that
+        uses it; a progenitor passed as h is one more operand array.  The int expressions are not counted (a caller's own elementwise passes)"""
+        w = (self.wl // 8) * self.params.nlimbs
+        total = 0
+        for o in self.ops:
+            op = o[0]
+            if op in _INT_OPS:
+                continue
+            arrays = _OPS[op] + (1 if op in _WITH_H and o[3] >= 0 else 0)
+            if op in _PREDS:
+                total += w * arrays + 4
+            else:
+                total += w * (arrays + (2 if op == "modcsw" else 1)) + (4 if op in ("modcmv", "modcsw") else 0)
+        return total
 
     def _body_lines(self) -> List[str]:
         """the chain as Field<P> calls on registers, one line per operation"""
         L = []
+        h_of = lambda h: "nullptr" if h < 0 else "v%d" % h
+        tested = set()                                        # values a predicate has read
         for o in self.ops:
             op, d, a, b, imm = o[:5]
+            if op in _PREDS and op != "modqr":
+                # Every predicate starts with redc of its operands.  A second one on the same value would share the pure part of that
+                # redc with the first (the products; the pinned accumulations are not shareable) and keep every partial product live
+                # in between: 392 instead of 72 registers for `modsign(u) ... modcmp(u, v)` over P-256.  It reads an opaque copy instead
+                pre, ab = "", [a, b]
+                for k, x in enumerate(ab):
+                    if x >= 0 and x in tested:
+                        pre += "spint t%d_%d[P::N]; opaque(v%d, t%d_%d); " % (d, k, x, d, k)
+                        ab[k] = "t%d_%d" % (d, k)
+                    elif x >= 0:
+                        tested.add(x)
+                        ab[k] = "v%d" % x
+                L.append("    %ss%d = F::%s(%s);" % (pre, d, op, ", ".join(x for x in ab if x != -1)))
+                continue
             if op == "modcsw":
                 L.append("    F::modcpy(v%d, v%d); F::modcpy(v%d, v%d); F::modcsw(s%d, v%d, v%d);" % (a, d, b, o[5], imm, d, o[5]))
             elif op == "modcmv":
@@ -267,9 +365,13 @@ class Chain:
             elif op == "modhaf":
                 L.append("    F::modcpy(v%d, v%d); F::modhaf(v%d);" % (a, d, d))
             elif op == "modsqrt":
-                L.append("    F::modsqrt(v%d, nullptr, v%d);" % (a, d))
+                L.append("    F::modsqrt(v%d, %s, v%d);" % (a, h_of(b), d))
             elif op == "modinv":
-                L.append("    F::modinv(v%d, nullptr, v%d); inv_normalise<F>(v%d);" % (a, d, d))
+                L.append("    F::modinv(v%d, %s, v%d); inv_normalise<F>(v%d);" % (a, h_of(b), d, d))
+            elif op == "modqr":
+                L.append("    s%d = F::modqr(%s, v%d);" % (d, h_of(b), a))
+            elif op in _INT_OPS:
+                L.append("    s%d = %s;" % (d, _INT_OPS[op] % ((a,) if b < 0 else (a, b))))
             elif op == "modmli":
                 L.append("    F::modmli(v%d, %d, v%d);" % (a, imm, d))
             elif op == "modint":
@@ -287,7 +389,7 @@ class Chain:
         kernels (k_chain<EPT>, k_chain_aos) and the bodies of the entry points for both word lengths.
         ept: elements per lane on aligned batches (2 = 16-byte accesses, 1 = 8-byte; at word length 32: 4 / 2 / 1 = 16 / 8 / 4 bytes);
         None = the measured default.  block: workgroup size, word length 32 only"""
-        if not self.nin or not self.outs:
+        if not self.nin or not (self.outs or self.pouts):
             raise ValueError("a chain needs at least one input and one output")
         P, nv, N, w32 = self.prime, self.nvals, self.params.nlimbs, self.wl == 32
         shared = set(self.sh_idx)                         # one element for the whole batch: a pointer into the kernel arguments, not a per-lane array
@@ -319,9 +421,11 @@ class Chain:
             shape = ["#define CHAIN_AOS_IMAGES %d   // LDS images of the element-major kernel: one per input array, 1 = one shared image, 0 = no kernel (more than 14 limbs)" % images]
         if shared:
             shape.append("#define CHAIN_NSHARED %d   // operands that are one element for the whole batch: host pointers after the element batches in in[], by value in the kernel arguments" % self.nshared)
+        if self.pouts:
+            shape.append("#define CHAIN_NPRED %d   // int32 results, one entry per element: device arrays after the element outputs in out[]" % len(self.pouts))
         if waves:
             shape.append("#define CHAIN_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(%d, %d)))" % (waves, waves))
-        args = ", ".join([("v%d" if i in shared else "v%d[E]") % i for i in range(nv)] + ["s%d[E]" % k for k in range(self.nsel)])
+        args = ", ".join([("v%d" if i in shared else "v%d[E]") % i for i in range(nv)] + ["s%d[E]" % k for k in range(self.nsel + self.npred)])
         # modint of a negative int is the word (spint)k, outside the limb contract at 64 bits: such a chain runs the exact products, as Field.modint does
         if policy == "vote" and any(o[0] == "modint" and o[4] < 0 for o in self.ops):
             policy = "exact"
@@ -339,23 +443,29 @@ class Chain:
                    "    } else {",
                    "        static_for<0, EPT>([&](auto E) { body<Field<P, false>>(%s); });" % args,
                    "    }"]
-        L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s%s: %d inputs%s, %d operations, %d outputs; kernels and entry bodies: csrc/chain.inc"
-             % (self.name, P, ", 32-bit word form" if w32 else "", self.nin, ", %d shared" % self.nshared if shared else "", len(self.ops), len(self.outs))]
+        L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s%s: %d inputs%s, %d operations, %d outputs%s; kernels and entry bodies: csrc/chain.inc"
+             % (self.name, P, ", 32-bit word form" if w32 else "", self.nin, ", %d shared" % self.nshared if shared else "", len(self.ops), len(self.outs), ", %d int outputs" % len(self.pouts) if self.pouts else "")]
         L += head + ['#define CHAIN_SYMBOL "%s"   // the entry points: <this>_batch%s' % (self.symbol[:-6], "" if w32 else ", <this>_aos"),
                      "constexpr int NIN = %d, NOUT = %d, NSEL = %d;" % (self.nin, len(self.outs), self.nsel),
                      "constexpr bool HEAVY = %s;   // one element per lane on every batch: an inversion, a progenitor or a square root in the chain%s"
                      % ("true" if heavy else "false", "" if w32 else ", or build(ept=1)")] + shape
         L += ["", "// the chain on one element's registers; F = %s" % ("Field<P> (one product policy at this word length: no vote)" if w32 else "Field<P, FAST>"),
-              "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i < self.nin + self.nshared else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)])]
-        L += self._body_lines()
+              "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i < self.nin + self.nshared else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)] + ["int& s%d" % (self.nsel + k) for k in range(self.npred)])]
+        body = self._body_lines()
+        if any("opaque(" in l for l in body):
+            L[-2:-2] = ["// a copy of an element that the compiler cannot see through (for a value that a second predicate reads: Chain._body_lines)",
+                        'MA_DEV void opaque(const spint* a, spint* c) { static_for<0, P::N>([&](auto I) { spint x = a[I]; asm volatile("" : "+v"(x)); c[I] = x; }); }', ""]
+        L += body
         L += ["}", "", "// EPT elements of a lane through the chain; io is how the calling kernel of csrc/chain.inc reaches them in memory",
               "template <int EPT, class IO> MA_DEV void chain_step(IO io) {",
               "    " + " ".join("spint v%d[EPT][P::N];" % i for i in range(nv) if i not in shared)]
         L += ["    io.load(%d, v%d);" % (k, i) for k, i in enumerate(self.in_idx)]
         L += ["    const spint* v%d = io.shared(%d);" % (i, k) for k, i in enumerate(self.sh_idx)]
         L += ["    int s%d[EPT]; io.sel(%d, s%d);" % (k, k, k) for k in range(self.nsel)]
+        L += ["    int s%d[EPT];" % (self.nsel + k) for k in range(self.npred)]
         L += run
         L += ["    io.store(%d, v%d);" % (k, o) for k, o in enumerate(self.outs)]
+        L += ["    io.pred(%d, s%d);" % (k, o) for k, o in enumerate(self.pouts)]
         L += ["}", '#include "chain.inc"', "}  // namespace", "",
               'extern "C" int %s(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) { return chain_batch(in, out, n, ld, stream); }' % self.symbol]
         if not w32:
@@ -383,15 +493,20 @@ class Chain:
         lib = self.lib_path(d)
         emit._write(src, src_text)
         record = {"chain": self.name, "prime": self.prime, "wl": self.wl, "inputs": self.nin, "shared": self.nshared, "selectors": self.nsel,
-                  "outputs": len(self.outs), "ops": [o[0] for o in self.ops], "symbol": self.symbol}
-        built = build_plugin(d, lib, meta, record, _gen.key_of(src_text, emit.header_text(self.params)), [(src, obj, [])], "chain", force, verbose)
+                  "outputs": len(self.outs), "preds": len(self.pouts), "ops": [o[0] for o in self.ops], "symbol": self.symbol}
+        # A chain that computes ints is compiled without the SLP vectoriser: at two elements per lane it pairs the limbs of the two elements'
+        # redc (they arrive as the halves of one 16-byte load) into vector operations and the kernel of four predicates over P-256 comes to
+        # 380 registers instead of 119.  Chains without ints are compiled as they always were
+        flags = ["-fno-slp-vectorize"] if self.npred else []
+        built = build_plugin(d, lib, meta, record, _gen.key_of(src_text, emit.header_text(self.params)), [(src, obj, flags)], "chain", force, verbose)
         return FusedChain(self, lib, built)
 
 
 class FusedChain:
     """a built chain: call it with one device batch per input (flat [N, n] or tiled [n / tile, N, tile], all the same shape; int64
     limbs, or int32 for a chain of the 32-bit word form), then one host element per shared operand (Nlimbs ints or a CPU integer
-    tensor, as Field.modmuls takes b0), then one int32 device array per selector"""
+    tensor, as Field.modmuls takes b0), then one int32 device array per selector.  Returns the element outputs, then one int32 [n]
+    tensor per int output (ch.output() of a Pred); `out=` takes them in that order"""
     def __init__(self, chain: Chain, lib: str, built: bool):
         self.chain, self.path, self.built = chain, lib, built
         _lib.load()
@@ -421,6 +536,15 @@ class FusedChain:
         word = ctypes.c_uint64 if ch.wl == 64 else ctypes.c_uint32
         return (word * len(b))(*[v & ((1 << ch.wl) - 1) for v in b])          # (signed tensors hold the same words)
 
+    def _outs(self, out, n: int, like, fresh):
+        """the arrays of out[]: the element outputs (fresh() each where the caller gives none), then one int32 [n] per int output"""
+        import torch
+        ch = self.chain
+        outs = list(out) if out is not None else [fresh() for _ in ch.outs] + [torch.empty(n, dtype=torch.int32, device=like.device) for _ in ch.pouts]
+        if len(outs) != len(ch.outs) + len(ch.pouts):
+            raise ValueError("chain %s has %d outputs%s" % (ch.name, len(ch.outs), " followed by %d int32 outputs" % len(ch.pouts) if ch.pouts else ""))
+        return outs
+
     def _run(self, fn, symbol: str, elems, shared, sels, outs, n: int, *ld, device=None):
         """what both entries share: the selector check, the pointer arrays and the call on the current stream of the batches' device.
         The entry point reads the shared operands' limbs before it returns: the host arrays need to live no longer than this call"""
@@ -429,6 +553,9 @@ class FusedChain:
             if d.dtype != torch.int32 or d.numel() != n or not d.is_cuda or not d.is_contiguous() or (device is not None and d.device != device):
                 raise ValueError("selectors are contiguous int32 device tensors with one 0/1 entry per element")
         dev = device if device is not None else elems[0].device
+        for d in outs[len(self.chain.outs):]:
+            if d.dtype != torch.int32 or d.dim() != 1 or d.numel() != n or not d.is_cuda or not d.is_contiguous() or d.device != dev:
+                raise ValueError("int outputs are contiguous int32 tensors of n entries on the batches' device")
         ptrs = [t.data_ptr() for t in elems] + [ctypes.addressof(b) for b in shared] + [t.data_ptr() for t in sels]
         ins = (ctypes.c_void_p * len(ptrs))(*ptrs)
         ous = (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
@@ -446,8 +573,8 @@ class FusedChain:
             raise ValueError("the element-major entry is not built at word length 32: convert with modarith_amd_w32_aos_to_soa and call %s" % ch.symbol)
         elems, shared, sels = self._split(inputs, "arrays")
         n = elems[0].shape[0]
-        outs = list(out) if out is not None else [torch.empty_like(elems[0]) for _ in ch.outs]
-        for t in list(elems) + outs:
+        outs = self._outs(out, n, elems[0], lambda: torch.empty_like(elems[0]))
+        for t in list(elems) + outs[:len(ch.outs)]:
             if t.dtype != torch.int64 or t.dim() != 2 or tuple(t.shape) != (n, N) or not t.is_cuda or not t.is_contiguous():
                 raise ValueError("expected contiguous int64 device tensors of shape [n, %d]" % N)
         fn = getattr(self.lib, ch.aos_symbol)
@@ -463,10 +590,9 @@ class FusedChain:
         F = self._fields.get(dev)
         if F is None:                                  # binding a Field derives the prime's constants: once per device, not per call
             F = self._fields[dev] = Field(ch.prime, dev, wl=ch.wl)
-        outs = list(out) if out is not None else [F._out(inputs[0], None) for _ in ch.outs]
-        if len(outs) != len(ch.outs):
-            raise ValueError("chain %s has %d outputs" % (ch.name, len(ch.outs)))
-        n = F._chk(*inputs, *outs)
+        n = F._chk(*inputs)
+        outs = self._outs(out, n, inputs[0], lambda: F._out(inputs[0], None))
+        n = F._chk(*inputs, *outs[:len(ch.outs)])
         return self._run(self.fn, ch.symbol, inputs, shared, sels, outs, n, F._ld(inputs[0]), device=F.device)
 
 
@@ -478,6 +604,62 @@ def bench_chain(prime: str = "X25519") -> Chain:
     return ch
 
 
+def internal_limbs(prime: str, v: int, wl: int = 64) -> List[int]:
+    """the value v as the limbs a shared operand takes: the field's internal form (times R for a Montgomery field), canonical"""
+    from .params import derive
+    fp = derive(prime, wl=wl)
+    v %= fp.p
+    return fp.to_limbs(v * fp.R % fp.p if fp.montgomery else v, masked_top=True)
+
+
+def oncurve_chain(curve: str = "NIST256", wl: int = 64, name: str = "oncurve"):
+    """"is (x, y) on the curve": modcmp(y^2, x^3 - 3x + b) for a short Weierstrass curve with a = -3 (the test of weierstrass.c's
+    setxy), b shared, ONE int32 per element out and no limb array.  Returns (chain, [limbs of b]); f(x, y, b) -> (ok,)"""
+    from .curves import wcurve
+    c = wcurve(curve)
+    if c.a != -3:
+        raise ValueError("oncurve_chain is written for a = -3 (got %s)" % curve)
+    ch = Chain(c.field, name, wl=wl)
+    x, y = ch.inputs(2)
+    b = ch.shared()
+    lhs = ch.modsqr(y)
+    ch.output(ch.modcmp(lhs, ch.modadd(ch.modsub(ch.modmul(ch.modsqr(x), x), ch.modmli(x, 3)), b)))
+    return ch, [internal_limbs(c.field, c.b, wl)]
+
+
+def decompress_chain(curve: str = "ED25519", wl: int = 64, name: str = "decompress"):
+    """point decompression, edwards.c:290-334 (ecnXXXset from y and the sign s of x) for a = -1 and a full-size d: x from
+    x^2 = (1 - y^2) / (-1 - d y^2) with ONE progenitor shared by modqr, modsqrt and modinv, the sign fixed by a computed selector, and a y
+    with no x turned into the point at infinity (0, 1, 1) by modcmv instead of the reference's early return.
+    Returns (chain, [limbs of d]); f(y, d, s) -> (x, y, z, ok), ok = the modqr test: 1 - isinf of the point (for y = 1, whose x is 0, the
+    point that was asked for IS the neutral element: ok = 1)"""
+    from .curves import curve as _curve
+    c = _curve(curve)
+    if c.a != -1 or c.small_b:
+        raise ValueError("decompress_chain is written for a = -1 and a full-size d (ED25519; got %s)" % curve)
+    ch = Chain(c.field, name, wl=wl)
+    y = ch.input()
+    d = ch.shared()
+    s = ch.selector()
+    one = ch.modone()
+    Y = ch.modsqr(y)
+    U = ch.modsub(one, Y)                                   # 1 - y^2
+    V = ch.modsub(ch.modneg(one), ch.modmul(Y, d))          # -1 - d y^2
+    O = ch.modsqr(U)
+    W = ch.modmul(ch.modmul(U, O), V)                       # U^3 V
+    H = ch.modpro(W)
+    ok = ch.modqr(W, H)
+    R = ch.modsqrt(W, H)
+    X = ch.modmul(ch.modmul(ch.modinv(W, H), R), O)
+    X = ch.modcmv(ch.lxor(ch.modsign(X), s), ch.modneg(X), X)        # (modsign(U) - s) & 1 on 0/1 ints
+    bad = ch.lnot(ok)
+    ch.output(ch.modcmv(bad, ch.modzer(), X))
+    ch.output(ch.modcmv(bad, one, y))
+    ch.output(ch.modcpy(one))
+    ch.output(ok)
+    return ch, [internal_limbs(c.field, c.d, wl)]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # command line: a chain written as text, for consumers that do not otherwise touch Python
 #   python -m modarith_amd.fuse 32 X25519 accept "..."        (the same chain over the 32-bit word form)
@@ -486,10 +668,14 @@ def parse(prime: str, name: str, text: str, wl: int = 64) -> Chain:
     """statements separated by ';':  `in a, b`  (element inputs, in order) | `shared b, d` (operands that are one element for the whole
     batch) | `sel d` (int32 selector inputs) | `v = f(args)` |
     `g2, f2 = modcsw(d, g, f)` | `out expr, ...`.  Expressions nest: modsqr(modmul(a, b)).  Integers are accepted where the
-    function takes one (modmli, modnsqr, modint); modone() and modzer() take nothing.  Function names are the chain's methods, i.e. field.c's."""
+    function takes one (modmli, modnsqr, modint); modone() and modzer() take nothing.  Function names are the chain's methods, i.e. field.c's.
+    The predicates (modis0, modis1, modsign, modcmp, modqr) give ints; `not d`, `d & e`, `d | e`, `d ^ e` are lnot / land / lor / lxor on
+    ints and selectors (0 / 1; `not` binds loosest: write `d & (not e)`); modsqrt(a, h), modinv(a, h), modqr(x, h) take the progenitor as
+    an optional second argument; `out` takes ints as well: int32 results after the element results."""
     import ast
     ch = Chain(prime, name, wl)
     env = {}
+    _INT_AST = {ast.BitAnd: "land", ast.BitOr: "lor", ast.BitXor: "lxor"}
 
     def ev(node):
         if isinstance(node, ast.Name):
@@ -500,6 +686,10 @@ def parse(prime: str, name: str, text: str, wl: int = 64) -> Chain:
             return node.value
         if isinstance(node, ast.UnaryOp) and isinstance(node.op, ast.USub) and isinstance(node.operand, ast.Constant):
             return -node.operand.value
+        if isinstance(node, ast.UnaryOp) and isinstance(node.op, ast.Not):
+            return ch.lnot(ev(node.operand))
+        if isinstance(node, ast.BinOp) and type(node.op) in _INT_AST:
+            return getattr(ch, _INT_AST[type(node.op)])(ev(node.left), ev(node.right))
         if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and not node.keywords:
             fn = node.func.id
             if fn not in _OPS or not hasattr(ch, fn):
@@ -555,9 +745,10 @@ def main(argv: List[str]) -> int:
         print(e)
         return 2
     print("%s %s" % ("built" if f.built else "up to date:", f.path))
-    print("int %s(const void *const *in /* %d element batches%s%s */, void *const *out /* %d */, size_t n, size_t ld, void *stream);"
+    print("int %s(const void *const *in /* %d element batches%s%s */, void *const *out /* %d%s */, size_t n, size_t ld, void *stream);"
           % (ch.symbol, ch.nin, (", then %d host pointers to shared operands of %d limbs" % (ch.nshared, ch.params.nlimbs)) if ch.nshared else "",
-             (", then %d int32 selector arrays" % ch.nsel) if ch.nsel else "", len(ch.outs)))
+             (", then %d int32 selector arrays" % ch.nsel) if ch.nsel else "", len(ch.outs),
+             (" element batches, then %d int32 arrays of n entries" % len(ch.pouts)) if ch.pouts else ""))
     if ch.wl == 64:
         print("int %s(const void *const *in, void *const *out, size_t n, void *stream);   /* the same over element-major arrays x[n][Nlimbs] */" % ch.aos_symbol)
     print("HBM bytes per element: %d fused, %d call by call" % (ch.traffic_bytes(), ch.unfused_traffic_bytes()))
