@@ -9,10 +9,13 @@
 //   #define CHAIN_KERNEL_ATTR __attribute__((...))                        optional: an occupancy hint on k_chain
 //   #define CHAIN_NSHARED k                                               optional: batch-wide element operands (ch.shared()), 1 .. 8
 //   #define CHAIN_NPRED k                                                 optional: int32 results (ch.output() of a Pred), one entry per element
+//   #define CHAIN_NBIN k, CHAIN_NBOUT k                                   optional: byte-record inputs (ch.input_bytes()) and outputs (ch.output_bytes())
+//   #define CHAIN_BYTES_STAGED 0 | 1                                      with either of them: the default way to the bytes (section "byte records")
 //   template <class F> MA_DEV void body(v0, ..., s0, ...);                the chain on one element's registers
 //   template <int EPT, class IO> MA_DEV void chain_step(IO io);           EPT elements of a lane: io.load(i, v_i) per input, io.shared(j)
 //                                                                         per shared operand, io.sel(k, s_k) per selector, the vote,
-//                                                                         body, io.store(k, v_o) per output, io.pred(k, s_j) per int output
+//                                                                         body, io.store(k, v_o) per output, io.pred(k, s_j) per int output;
+//                                                                         io.imp(j, v, s) per byte input, io.exp(k, v) per byte output
 // and then defines its `extern "C"` symbols over chain_batch() and chain_aos().  Editing this file rebuilds every chain (generate.key_of
 // hashes all of csrc/).
 #if MA_WL == 32
@@ -48,7 +51,17 @@ static_assert(CHAIN_NSHARED >= 0 && CHAIN_NSHARED <= 8, "a chain takes at most 8
 #ifndef CHAIN_NPRED
 #define CHAIN_NPRED 0
 #endif
-static_assert(CHAIN_NPRED >= 0 && NOUT + CHAIN_NPRED > 0, "a chain returns at least one array");
+// Byte records (CHAIN_NBIN + CHAIN_NBOUT > 0): arrays of n big-endian records of P::NBYTES bytes, rec[j * NBYTES + i], what modimp reads and
+// modexp writes; record index = element index.  The kernels and the entry of such a chain are in the section "byte records" below; with
+// both 0 nothing of it is compiled and this file is what it was.
+#ifndef CHAIN_NBIN
+#define CHAIN_NBIN 0
+#endif
+#ifndef CHAIN_NBOUT
+#define CHAIN_NBOUT 0
+#endif
+static_assert(CHAIN_NBIN >= 0 && CHAIN_NBOUT >= 0 && NIN + CHAIN_NBIN > 0, "a chain reads at least one array");
+static_assert(CHAIN_NPRED >= 0 && NOUT + CHAIN_NPRED + CHAIN_NBOUT > 0, "a chain returns at least one array");
 #if CHAIN_NPRED > 0
 #define CHAIN_PRED_ARGS int* pred[CHAIN_NPRED];
 #else
@@ -83,6 +96,225 @@ __global__ __launch_bounds__(CBLOCK) CHAIN_KERNEL_ATTR void k_chain(Args A, size
     for (size_t t = (size_t)blockIdx.x * CBLOCK + threadIdx.x; t < nthreads; t += (size_t)gridDim.x * CBLOCK) chain_step<EPT>(SoaIO<EPT>{A, L, t});
 }
 
+#if CHAIN_NBIN + CHAIN_NBOUT > 0
+// ---- byte records: modimp at the head of the chain and modexp at its tail, inside the kernel.  io.imp(j, v, s) leaves in v the CANONICAL
+// limbs of the integer that record j spells (limbs_from_words, then modfsb: inside the limb contract, so an imported value joins the
+// vote as any input does) and in s modimp's return value; the chain's body starts with F::nres of it, under the policy the wave voted
+// for.  The body ends with F::redc of what io.exp(k, v) then turns into bytes (words_from_limbs and the store).  Two ways to the bytes:
+//   direct   every lane reads and writes its own records in HBM, as k_imp / k_exp do (load_be_record / store_be_record of kernels.h).
+//            Always legal: the remainder launch and any call whose record arrays are not 16-byte aligned take it;
+//   staged   a workgroup moves the records of the CBLOCK * EPT consecutive elements it is about to process -- one linear stretch,
+//            16-byte aligned since 64 * NBYTES is a multiple of 16 -- with 16-byte-per-lane coalesced non-temporal accesses into an
+//            LDS image, and after a barrier every lane takes its own records out of the image (the same load_be_record, on LDS);
+//            output is the mirror image.  A record's pitch in the image is an odd number of 8-byte words where NBYTES is a
+//            multiple of 8 and of 4-byte words otherwise: a wave's accesses conflict two ways at the most (the idea of SP = N | 1
+//            below).  One image per byte input while they fit 64 KB together, else one image that the arrays take in turn between
+//            barriers (the CHAIN_AOS_IMAGES rule); the outputs go through the first image.
+// Which of the two a call on aligned arrays takes is BYTES_STAGED below (measured: tools/chain_bytes_rate.py, docs/fused_chains.md);
+// the environment variable MA_CHAIN_BYTES=staged|direct, read at every call, overrides it (tests, the rate tool).
+struct BArgs { const unsigned char* bin[CHAIN_NBIN > 0 ? CHAIN_NBIN : 1]; unsigned char* bout[CHAIN_NBOUT > 0 ? CHAIN_NBOUT : 1]; };
+constexpr int NB = P::NBYTES, NW = Field<P>::NW;
+constexpr bool BYTES_STAGED = CHAIN_BYTES_STAGED; // the path of a call on 16-byte aligned record arrays: the unit says (fuse.BYTES_IO_DEFAULT)
+MA_DEV int imp_words(const word_t* w, spint* v) {
+    Field<P>::limbs_from_words(w, v);
+    return (int)Field<P>::modfsb(v);
+}
+
+template <int EPT> struct ByteIO : SoaIO<EPT> {       // direct: records EPT t .. EPT t + EPT - 1 of lane t, at their place in HBM
+    const BArgs& B;
+    MA_DEV void imp(int j, spint (*v)[P::N], int* s) const {
+        static_for<0, EPT>([&](auto E) {
+            word_t w[NW];
+            load_be_record<P>(B.bin[j], (size_t)EPT * this->t + E, w);
+            s[E] = imp_words(w, v[E]);
+        });
+    }
+    MA_DEV void exp(int k, spint (*v)[P::N]) const {
+        static_for<0, EPT>([&](auto E) {
+            word_t w[NW];
+            Field<P>::words_from_limbs(v[E], w);
+            store_be_record<P>(B.bout[k], (size_t)EPT * this->t + E, w);
+        });
+    }
+};
+template <int EPT>
+__global__ __launch_bounds__(CBLOCK) CHAIN_KERNEL_ATTR void k_chain_direct(Args A, BArgs B, size_t nthreads, Ld L) {
+    for (size_t t = (size_t)blockIdx.x * CBLOCK + threadIdx.x; t < nthreads; t += (size_t)gridDim.x * CBLOCK) chain_step<EPT>(ByteIO<EPT>{{A, L, t}, B});
+}
+
+// the LDS image of a stretch of records: UNIT bytes are what is moved in one piece (a record's 8-byte words, or its bytes), PITCH the
+// bytes from one record to the next
+constexpr int UNIT = NB % 8 == 0 ? 8 : 1, UPR = NB / UNIT;
+constexpr int PITCH = UNIT == 8 ? (UPR | 1) * 8 : (((NB + 3) / 4) | 1) * 4;
+constexpr int image_bytes(int ept) { return CBLOCK * ept * PITCH; }
+constexpr int images(int ept) { return CHAIN_NBIN > 1 && CHAIN_NBIN * image_bytes(ept) <= 65536 ? CHAIN_NBIN : 1; }
+constexpr bool STAGED_BUILT = image_bytes(EPT_BUILT) <= 65536;        // (a record too long for one image: the direct path only)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+// `total` bytes at src (16-byte aligned) into the image: 16 bytes a lane and step, what is left of the last 16 byte by byte
+MA_DEV void stage_in(const unsigned char* src, unsigned total, unsigned char* img) {
+    for (unsigned o = 16u * threadIdx.x; o + 16 <= total; o += 16u * CBLOCK) {
+        const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src + o));
+        unsigned r = (o / UNIT) / UPR, i = (o / UNIT) % UPR;
+        static_for<0, 16 / UNIT>([&](auto U) {
+            constexpr int u = U;
+            if constexpr (UNIT == 8) *reinterpret_cast<word_t*>(img + r * PITCH + i * 8) = (word_t)x[2 * u] | (word_t)x[2 * u + 1] << 32;
+            else img[r * PITCH + i] = (unsigned char)(x[u / 4] >> (8 * (u % 4)));
+            if (++i == UPR) { i = 0; r++; }
+        });
+    }
+    for (unsigned o = (total & ~15u) + threadIdx.x; o < total; o += CBLOCK) img[(o / NB) * PITCH + o % NB] = src[o];
+}
+MA_DEV void stage_out(unsigned char* dst, unsigned total, const unsigned char* img) {
+    for (unsigned o = 16u * threadIdx.x; o + 16 <= total; o += 16u * CBLOCK) {
+        u32x4 x = {0, 0, 0, 0};
+        unsigned r = (o / UNIT) / UPR, i = (o / UNIT) % UPR;
+        static_for<0, 16 / UNIT>([&](auto U) {
+            constexpr int u = U;
+            if constexpr (UNIT == 8) {
+                const word_t w = *reinterpret_cast<const word_t*>(img + r * PITCH + i * 8);
+                x[2 * u] = (uint32_t)w; x[2 * u + 1] = (uint32_t)(w >> 32);
+            } else {
+                x[u / 4] |= (uint32_t)img[r * PITCH + i] << (8 * (u % 4));
+            }
+            if (++i == UPR) { i = 0; r++; }
+        });
+        __builtin_nontemporal_store(x, reinterpret_cast<u32x4*>(dst + o));
+    }
+    for (unsigned o = (total & ~15u) + threadIdx.x; o < total; o += CBLOCK) dst[o] = img[(o / NB) * PITCH + o % NB];
+}
+template <int... I> MA_DEV void stage_in_all(const BArgs& B, size_t first, unsigned total, unsigned char* sh, int image, std::integer_sequence<int, I...>) {
+    (stage_in(B.bin[I] + first, total, sh + I * image), ...);
+}
+// staged: the workgroup's lanes are t0 .. t0 + CBLOCK - 1, the first cnt of them have elements.  The others take every barrier, compute
+// on zeros (inside the limb contract: they vote with the wave) and store nothing, as the lanes beyond cnt of AosIO
+template <int EPT> struct StagedIO {
+    const Args& A; const BArgs& B; Ld L; size_t t0; unsigned cnt; unsigned char* sh;
+    MA_DEV bool live() const { return threadIdx.x < cnt; }
+    MA_DEV size_t t() const { return t0 + threadIdx.x; }
+    MA_DEV size_t first() const { return t0 * EPT * NB; }                                  // the stretch of this workgroup in a record array
+    MA_DEV unsigned char* mine(unsigned char* img, int e) const { return img + (threadIdx.x * EPT + e) * PITCH; }
+    MA_DEV void load(int i, spint (*v)[P::N]) const {
+        if (live()) load_soa<P, EPT>(A.in[i], L, t(), v);
+        else static_for<0, EPT>([&](auto E) { static_for<0, P::N>([&](auto I) { v[E][I] = 0; }); });
+    }
+    MA_DEV const spint* shared(int j) const { return shared_of(A, j); }
+    MA_DEV void sel(int k, int* s) const { static_for<0, EPT>([&](auto E) { s[E] = live() ? A.sel[k][(size_t)EPT * t() + E] : 0; }); }
+    MA_DEV void store(int k, spint (*v)[P::N]) const { if (live()) store_soa<P, EPT>(A.out[k], L, t(), v); }
+#if CHAIN_NPRED > 0
+    MA_DEV void pred(int k, const int* s) const { static_for<0, EPT>([&](auto E) { if (live()) A.pred[k][(size_t)EPT * t() + E] = s[E]; }); }
+#endif
+    MA_DEV void imp(int j, spint (*v)[P::N], int* s) const {
+        unsigned char* img = sh;
+        if constexpr (images(EPT) == CHAIN_NBIN) {
+            img += j * image_bytes(EPT);                  // (k_chain_staged has filled the images)
+        } else {
+            __syncthreads();                              // the previous user of the image is done
+            stage_in(B.bin[j] + first(), cnt * EPT * NB, img);
+            __syncthreads();
+        }
+        static_for<0, EPT>([&](auto E) {
+            word_t w[NW];
+            if (live()) load_be_record<P>(mine(img, E), 0, w);
+            else static_for<0, NW>([&](auto K) { w[K] = 0; });
+            s[E] = imp_words(w, v[E]);
+        });
+    }
+    MA_DEV void exp(int k, spint (*v)[P::N]) const {
+        __syncthreads();
+        static_for<0, EPT>([&](auto E) {
+            word_t w[NW];
+            Field<P>::words_from_limbs(v[E], w);
+            if (live()) store_be_record<P>(mine(sh, E), 0, w);
+        });
+        __syncthreads();
+        stage_out(B.bout[k] + first(), cnt * EPT * NB, sh);
+    }
+};
+// the loop is on the workgroup's base lane: block-uniform, since barriers sit inside it
+template <int EPT>
+__global__ __launch_bounds__(CBLOCK) CHAIN_KERNEL_ATTR void k_chain_staged(Args A, BArgs B, size_t nthreads, Ld L) {
+    __shared__ __attribute__((aligned(16))) unsigned char sh[images(EPT) * image_bytes(EPT)];
+    for (size_t t0 = (size_t)blockIdx.x * CBLOCK; t0 < nthreads; t0 += (size_t)gridDim.x * CBLOCK) {
+        const unsigned cnt = nthreads - t0 < (size_t)CBLOCK ? (unsigned)(nthreads - t0) : (unsigned)CBLOCK;
+        if constexpr (CHAIN_NBIN > 0 && images(EPT) == CHAIN_NBIN) {
+            __syncthreads();
+            stage_in_all(B, t0 * EPT * NB, cnt * EPT * NB, sh, image_bytes(EPT), std::make_integer_sequence<int, CHAIN_NBIN>());
+            __syncthreads();
+        }
+        chain_step<EPT>(StagedIO<EPT>{A, B, L, t0, cnt, sh});
+    }
+}
+template <int EPT> void launch_bytes(bool staged, const Args& A, const BArgs& B, size_t nt, Ld L, bool tiled, hipStream_t s) {
+    if constexpr (STAGED_BUILT) if (staged) { k_chain_staged<EPT><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, B, nt, L); return; }
+    k_chain_direct<EPT><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, B, nt, L);
+}
+
+// in[0 .. NIN): element batches; then CHAIN_NBIN arrays of n byte records; then CHAIN_NSHARED host pointers; then NSEL int32 selector arrays
+// out[0 .. NOUT): element batches; then CHAIN_NBOUT arrays of n byte records; then CHAIN_NPRED int32 arrays of n entries
+// Record arrays are 8-byte aligned where NBYTES is a multiple of 8 (the rule of modimp_<P>_batch) and may be anywhere otherwise; a byte
+// output may be the array of a byte input.  ld is ignored by a chain without element arrays.  (The _batch symbol of a unit with byte
+// records calls this entry, not the one below.)
+int chain_bytes_batch(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) {
+    if (n == 0) return 0;
+    constexpr bool elems = NIN + NOUT > 0;
+    Ld L(elems ? ld : n);
+    if (elems && ld < n) {
+        if (ld < 128 || (ld & (ld - 1)) != 0) { set_error(CHAIN_SYMBOL "_batch: a limb stride below n selects the tiled layout and must be a power of two >= 128"); return (int)hipErrorInvalidValue; }
+        L = Ld(ld, (unsigned)__builtin_ctzll((unsigned long long)ld));
+    }
+    Args A;
+    BArgs B;
+    uintptr_t addr = 0, baddr = 0;
+    for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; addr |= reinterpret_cast<uintptr_t>(in[i]); }
+    for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; addr |= reinterpret_cast<uintptr_t>(out[i]); }
+    for (int i = 0; i < CHAIN_NBIN; i++) { B.bin[i] = (const unsigned char*)in[NIN + i]; baddr |= reinterpret_cast<uintptr_t>(in[NIN + i]); }
+    for (int i = 0; i < CHAIN_NBOUT; i++) { B.bout[i] = (unsigned char*)out[NOUT + i]; baddr |= reinterpret_cast<uintptr_t>(out[NOUT + i]); }
+    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + CHAIN_NBIN + CHAIN_NSHARED + i];
+#if CHAIN_NPRED > 0
+    for (int i = 0; i < CHAIN_NPRED; i++) A.pred[i] = (int*)out[NOUT + CHAIN_NBOUT + i];
+#endif
+    shared_from_host(A, in + CHAIN_NBIN);
+    if (NB % 8 == 0 && (baddr & 7u)) { set_error(CHAIN_SYMBOL "_batch: byte records must be 8-byte aligned"); return (int)hipErrorInvalidValue; }
+    bool staged = BYTES_STAGED;
+    if (const char* v = getenv("MA_CHAIN_BYTES")) {
+        const std::string m(v);
+        if (m == "staged") staged = true;
+        else if (m == "direct") staged = false;
+        else { set_error(CHAIN_SYMBOL "_batch: MA_CHAIN_BYTES is staged or direct"); return (int)hipErrorInvalidValue; }
+    }
+    staged = staged && (baddr & 15u) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    const bool tiled = L.s != 63;
+    // elements per lane: the rules of the entry without byte records, on the element arrays (a record array asks nothing of the width)
+    size_t e = EPT_CAP;
+    while (e > 1 && !(n >= e && (!elems || ld % e == 0) && (addr & (e * sizeof(spint) - 1)) == 0)) e /= 2;
+    const size_t nt = n / e, done = nt * e;
+    if constexpr (EPT_BUILT >= 4) if (e == 4) launch_bytes<4>(staged, A, B, nt, L, tiled, s);
+    if constexpr (EPT_BUILT >= 2) if (e == 2) launch_bytes<2>(staged, A, B, nt, L, tiled, s);
+    if (e == 1) launch_bytes<1>(staged, A, B, nt, L, tiled, s);
+    if (done < n) {                                   // fewer than e elements, at records that need not be 16-byte aligned: direct
+        const size_t o = L.off<P::N>(done);
+        Args A2 = A;
+        BArgs B2;
+        for (int i = 0; i < NIN; i++) A2.in[i] = A.in[i] + o;
+        for (int i = 0; i < NOUT; i++) A2.out[i] = A.out[i] + o;
+        for (int i = 0; i < NSEL; i++) A2.sel[i] = A.sel[i] + done;
+#if CHAIN_NPRED > 0
+        for (int i = 0; i < CHAIN_NPRED; i++) A2.pred[i] = A.pred[i] + done;
+#endif
+        for (int i = 0; i < CHAIN_NBIN; i++) B2.bin[i] = B.bin[i] + done * NB;
+        for (int i = 0; i < CHAIN_NBOUT; i++) B2.bout[i] = B.bout[i] + done * NB;
+        k_chain_direct<1><<<1, CBLOCK, 0, s>>>(A2, B2, n - done, Ld(L.ld));
+    }
+    return check_launch(CHAIN_SYMBOL "_batch");
+}
+#if MA_WL == 64
+int chain_aos(const void* const*, void* const*, size_t, void*) {        // byte records have no layout: _batch is the entry
+    set_error(CHAIN_SYMBOL "_aos: a chain with byte records has no element-major entry; call " CHAIN_SYMBOL "_batch");
+    return (int)hipErrorInvalidValue;
+}
+#endif
+#else
 // in[0 .. NIN): element batches; then CHAIN_NSHARED host pointers, one per shared operand; then NSEL int32 selector arrays, one entry per element
 // out[0 .. NOUT): element batches; then CHAIN_NPRED int32 arrays of n entries
 int chain_batch(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) {
@@ -125,6 +357,7 @@ int chain_batch(const void* const* in, void* const* out, size_t n, size_t ld, vo
     }
     return check_launch(CHAIN_SYMBOL "_batch");
 }
+#endif  // no byte records
 
 #if defined(CHAIN_AOS_IMAGES) && CHAIN_AOS_IMAGES > 0
 // ---- element-major I/O: x[n][N] in, x[n][N] out (how the scalar callers of field.c hold their elements).  A workgroup of 256 lanes

@@ -43,6 +43,18 @@ the int32 arrays (n contiguous entries each, indexed by element for flat and til
 of a selector input: a lane reads its entries before it stores), and a chain may have no other output: `oncurve_chain()` below reads two
 coordinate arrays and writes 4 bytes per element, `decompress_chain()` is edwards.c:290-334 as one kernel.
 
+A chain can speak bytes: `v, ok = ch.input_bytes()` is a byte-record input -- uint8 [n, Nbytes], big-endian, the layout of modimp_<P>_batch --
+with v what Field.modimp leaves (the integer the bytes spell, modfsb, nres) and ok its return value as a `Pred` (1 where the integer was
+below p); `ch.output_bytes(v)` is a byte-record output, modexp(v).  modimp and modexp then run inside the kernel: `c = a * b` on wire values
+moves 96 bytes an element over X25519 where the four calls move 344.  `in`: the element batches, then the record arrays, then the shared
+host pointers, then the selector arrays; `out`: the element arrays, then the record arrays, then the int32 arrays; the Python call takes
+and returns them in that order.  Records are 8-byte aligned where Nbytes is a multiple of 8 (the rule of modimp_<P>_batch) and may be
+anywhere otherwise; a byte output may be the array of a byte input.  A chain needs at least one element batch or one byte input: without
+element arrays on either side `ld` is ignored.  There is no element-major entry for such a chain (`_aos` refuses).  `pubkey_chain()` below
+checks an uncompressed P-256 public key as it arrives, 64 bytes in and 4 out.  Out of scope: little-endian records (the RFC 7748 / RFC 8032
+wire formats: the reference reverses them on the host), taking a sign bit out of a record, modshl / modshr / mod2r.  docs/fused_chains.md,
+"Chains that speak bytes", has the kernels' two ways to the bytes and their rates.
+
 Word length 32: `Chain(prime, name, wl=32)` is the same chain over the 32-bit word form of X25519, NIST256 and X448 (csrc/kernels32.h,
 namespace ma32; int32 batches of `Field(prime, wl=32)`): what a port of the reference's per-thread CUDA form (simd/pseudo_cuda.py 32)
 runs per element.  One product policy, so no vote; one, two or four elements per lane (the library's pick_ept rules), by default one
@@ -83,6 +95,10 @@ MAX_SHARED = 8                                    # shared operands of a chain: 
 # two and 0.728 / 0.752 / 0.697 at four elements per lane, workgroups of 128 behind 256 at every width -- the streaming kernels'
 # shape, ahead for X25519 and X448 and 1.3 % behind two elements per lane for NIST256.  build(ept=, block=) overrides them
 W32_EPT_DEFAULT = 1
+# Byte records (input_bytes / output_bytes): which of the two ways to the bytes of csrc/chain.inc a call on 16-byte aligned record arrays
+# takes, per word length.  Measured (tools/chain_bytes_rate.py, profiles/chain_bytes_rate.json, docs/fused_chains.md); the environment
+# variable MA_CHAIN_BYTES=staged|direct overrides it at every call
+BYTES_IO_DEFAULT = {64: "direct", 32: "direct"}
 W32_BLOCK_DEFAULT = 256
 
 
@@ -131,6 +147,8 @@ class Chain:
         self.npred = 0                      # ints computed inside the chain (Pred): s<nsel> .. s<nsel + npred - 1>
         self.pouts: List[int] = []          # the ints that are outputs (indices of the int space), in the order of out[] after the element outputs
         self.nvals = 0
+        self.bins: List[tuple] = []         # byte-record inputs: (the value modimp leaves, its flag's place among the computed ints), in the order of in[]
+        self.bouts: List[tuple] = []        # byte-record outputs: (the value, the value that holds its redc), in the order of out[]
 
     # ------------------------------------------------------------------ building
     def _new(self) -> Val:
@@ -159,6 +177,23 @@ class Chain:
     @property
     def nshared(self) -> int:
         return len(self.sh_idx)
+
+    def input_bytes(self):
+        """a byte-record input: n records of Nbytes big-endian bytes, after the element batches in in[].  Returns (v, ok): v is what
+        Field.modimp leaves (the integer the bytes spell, modfsb, nres), ok its return value as a Pred: 1 where the integer was below p"""
+        if self.ops:
+            raise ValueError("declare every input before the first operation")
+        v, ok = self._new(), Pred(self, self.npred)
+        self.npred += 1
+        self.bins.append((v.idx, ok.idx))
+        return v, ok
+
+    def output_bytes(self, v: Val) -> None:
+        """a byte-record output, modexp(v): redc, then Nbytes big-endian bytes a record, after the element outputs in out[]"""
+        self._own(v)
+        if v.idx in self.sh_idx:
+            raise ValueError("a shared operand is not a per-element array: output_bytes modcpy() of it")
+        self.bouts.append((v.idx, self._new().idx))
 
     def inputs(self, k: int) -> List[Val]:
         return [self.input() for _ in range(k)]
@@ -317,13 +352,15 @@ class Chain:
     def traffic_bytes(self) -> int:
         """HBM bytes per element of the fused kernel; the call-by-call sequence moves sum(w N (operands + 1)) instead (w = 8 or 4 bytes a limb).
         A shared operand costs the fused kernel nothing (it is in the kernel arguments); call by call it is an array like any other operand"""
-        return (self.wl // 8) * self.params.nlimbs * (self.nin + len(self.outs)) + 4 * self.nsel + 4 * len(self.pouts)
+        return ((self.wl // 8) * self.params.nlimbs * (self.nin + len(self.outs)) + 4 * self.nsel + 4 * len(self.pouts)
+                + self.params.nbytes * (len(self.bins) + len(self.bouts)))
 
     def unfused_traffic_bytes(self) -> int:
         """a predicate call reads its operand arrays and writes 4 bytes; a selector, streamed in or computed, is a 4-byte read of the call that
-        uses it; a progenitor passed as h is one more operand array.  The int expressions are not counted (a caller's own elementwise passes)"""
+        uses it; a progenitor passed as h is one more operand array.  The int expressions are not counted (a caller's own elementwise passes).
+        A byte input is a modimp call (Nbytes in, an element and the 4-byte flag out), a byte output a modexp call"""
         w = (self.wl // 8) * self.params.nlimbs
-        total = 0
+        total = len(self.bins) * (self.params.nbytes + w + 4) + len(self.bouts) * (w + self.params.nbytes)
         for o in self.ops:
             op = o[0]
             if op in _INT_OPS:
@@ -337,7 +374,7 @@ class Chain:
 
     def _body_lines(self) -> List[str]:
         """the chain as Field<P> calls on registers, one line per operation"""
-        L = []
+        L = ["    F::nres(v%d, v%d);" % (i, i) for i, _ in self.bins]      # io.imp() left the canonical limbs: the rest of modimp, on the voted products
         h_of = lambda h: "nullptr" if h < 0 else "v%d" % h
         tested = set()                                        # values a predicate has read
         for o in self.ops:
@@ -382,16 +419,18 @@ class Chain:
                 L.append("    F::%s(v%d, v%d, v%d);" % (op, a, b, d))
             else:
                 L.append("    F::%s(v%d, v%d);" % (op, a, d))
-        return L
+        return L + ["    F::redc(v%d, v%d);" % (a, d) for a, d in self.bouts]            # the first half of modexp; io.exp() makes the bytes
 
     def source(self, ept: Optional[int] = None, policy: str = "vote", waves: int = 0, block: Optional[int] = None) -> str:
         """The unit: what depends on the chain -- constants, body<F> and chain_step<EPT, IO> -- around csrc/chain.inc, which holds the
         kernels (k_chain<EPT>, k_chain_aos) and the bodies of the entry points for both word lengths.
         ept: elements per lane on aligned batches (2 = 16-byte accesses, 1 = 8-byte; at word length 32: 4 / 2 / 1 = 16 / 8 / 4 bytes);
         None = the measured default.  block: workgroup size, word length 32 only"""
-        if not self.nin or not (self.outs or self.pouts):
+        if not (self.nin or self.bins) or not (self.outs or self.pouts or self.bouts):
             raise ValueError("a chain needs at least one input and one output")
+        nbytes = len(self.bins) + len(self.bouts)
         P, nv, N, w32 = self.prime, self.nvals, self.params.nlimbs, self.wl == 32
+        consts = set(self.in_idx) | set(self.sh_idx)      # what the body only reads: the element inputs and the shared operands
         shared = set(self.sh_idx)                         # one element for the whole batch: a pointer into the kernel arguments, not a per-lane array
         if w32:
             if policy != "vote":
@@ -418,11 +457,18 @@ class Chain:
             images = 0 if N > 14 else self.nin if self.nin * 512 * (N | 1) * 8 <= 65536 else 1
             head = ['#include "params_%s.h"' % P, '#include "modarith_amd.h"', '#include "capi_common.h"', '#include "kernels.h"', "#include <utility>", "",
                     "namespace {", "using namespace ma;", "using P = ma::P_%s;" % P]
-            shape = ["#define CHAIN_AOS_IMAGES %d   // LDS images of the element-major kernel: one per input array, 1 = one shared image, 0 = no kernel (more than 14 limbs)" % images]
+            shape = [] if nbytes else ["#define CHAIN_AOS_IMAGES %d   // LDS images of the element-major kernel: one per input array, 1 = one shared image, 0 = no kernel (more than 14 limbs)" % images]
         if shared:
             shape.append("#define CHAIN_NSHARED %d   // operands that are one element for the whole batch: host pointers after the element batches in in[], by value in the kernel arguments" % self.nshared)
         if self.pouts:
             shape.append("#define CHAIN_NPRED %d   // int32 results, one entry per element: device arrays after the element outputs in out[]" % len(self.pouts))
+        if self.bins:
+            shape.append("#define CHAIN_NBIN %d   // byte-record inputs: arrays of n records of P::NBYTES big-endian bytes after the element batches in in[]" % len(self.bins))
+        if nbytes:
+            shape.append("#define CHAIN_BYTES_STAGED %d   // the way to the bytes of a call on 16-byte aligned record arrays: 1 = staged through LDS, 0 = direct (fuse.BYTES_IO_DEFAULT)"
+                         % (BYTES_IO_DEFAULT[self.wl] == "staged"))
+        if self.bouts:
+            shape.append("#define CHAIN_NBOUT %d   // byte-record outputs: arrays of n records after the element outputs in out[]" % len(self.bouts))
         if waves:
             shape.append("#define CHAIN_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(%d, %d)))" % (waves, waves))
         args = ", ".join([("v%d" if i in shared else "v%d[E]") % i for i in range(nv)] + ["s%d[E]" % k for k in range(self.nsel + self.npred)])
@@ -435,7 +481,7 @@ class Chain:
             run = ["    bool fast = %s;" % ("true" if policy == "fast" else "false"),
                    "    if constexpr (P::SPLIT > 0 && %s) {" % ("true" if policy == "vote" else "false"),
                    "        bool ok = %s;" % (" && ".join("in_split_contract<P>(v%d)" % i for i in self.sh_idx) or "true"),
-                   "        static_for<0, EPT>([&](auto E) { ok = ok && " + " && ".join("in_split_contract<P>(v%d[E])" % i for i in self.in_idx) + "; });",
+                   "        static_for<0, EPT>([&](auto E) { ok = ok && " + " && ".join("in_split_contract<P>(v%d[E])" % i for i in self.in_idx + [b[0] for b in self.bins]) + "; });",
                    "        fast = __all(ok);",
                    "    }",
                    "    if (fast) {",
@@ -444,13 +490,13 @@ class Chain:
                    "        static_for<0, EPT>([&](auto E) { body<Field<P, false>>(%s); });" % args,
                    "    }"]
         L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s%s: %d inputs%s, %d operations, %d outputs%s; kernels and entry bodies: csrc/chain.inc"
-             % (self.name, P, ", 32-bit word form" if w32 else "", self.nin, ", %d shared" % self.nshared if shared else "", len(self.ops), len(self.outs), ", %d int outputs" % len(self.pouts) if self.pouts else "")]
+             % (self.name, P, ", 32-bit word form" if w32 else "", self.nin, ", %d shared" % self.nshared if shared else "", len(self.ops), len(self.outs), (", %d int outputs" % len(self.pouts) if self.pouts else "") + (", %d byte inputs, %d byte outputs" % (len(self.bins), len(self.bouts)) if nbytes else ""))]
         L += head + ['#define CHAIN_SYMBOL "%s"   // the entry points: <this>_batch%s' % (self.symbol[:-6], "" if w32 else ", <this>_aos"),
                      "constexpr int NIN = %d, NOUT = %d, NSEL = %d;" % (self.nin, len(self.outs), self.nsel),
                      "constexpr bool HEAVY = %s;   // one element per lane on every batch: an inversion, a progenitor or a square root in the chain%s"
                      % ("true" if heavy else "false", "" if w32 else ", or build(ept=1)")] + shape
         L += ["", "// the chain on one element's registers; F = %s" % ("Field<P> (one product policy at this word length: no vote)" if w32 else "Field<P, FAST>"),
-              "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i < self.nin + self.nshared else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)] + ["int& s%d" % (self.nsel + k) for k in range(self.npred)])]
+              "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i in consts else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)] + ["int& s%d" % (self.nsel + k) for k in range(self.npred)])]
         body = self._body_lines()
         if any("opaque(" in l for l in body):
             L[-2:-2] = ["// a copy of an element that the compiler cannot see through (for a value that a second predicate reads: Chain._body_lines)",
@@ -463,11 +509,13 @@ class Chain:
         L += ["    const spint* v%d = io.shared(%d);" % (i, k) for k, i in enumerate(self.sh_idx)]
         L += ["    int s%d[EPT]; io.sel(%d, s%d);" % (k, k, k) for k in range(self.nsel)]
         L += ["    int s%d[EPT];" % (self.nsel + k) for k in range(self.npred)]
+        L += ["    io.imp(%d, v%d, s%d);" % (k, i, self.nsel + f) for k, (i, f) in enumerate(self.bins)]
         L += run
         L += ["    io.store(%d, v%d);" % (k, o) for k, o in enumerate(self.outs)]
+        L += ["    io.exp(%d, v%d);" % (k, t) for k, (_, t) in enumerate(self.bouts)]
         L += ["    io.pred(%d, s%d);" % (k, o) for k, o in enumerate(self.pouts)]
         L += ["}", '#include "chain.inc"', "}  // namespace", "",
-              'extern "C" int %s(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) { return chain_batch(in, out, n, ld, stream); }' % self.symbol]
+              'extern "C" int %s(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) { return %s(in, out, n, ld, stream); }' % (self.symbol, "chain_bytes_batch" if nbytes else "chain_batch")]
         if not w32:
             L += ['extern "C" int %s(const void* const* in, void* const* out, size_t n, void* stream) { return chain_aos(in, out, n, stream); }' % self.aos_symbol]
         return "\n".join(L + [""])
@@ -494,6 +542,8 @@ class Chain:
         emit._write(src, src_text)
         record = {"chain": self.name, "prime": self.prime, "wl": self.wl, "inputs": self.nin, "shared": self.nshared, "selectors": self.nsel,
                   "outputs": len(self.outs), "preds": len(self.pouts), "ops": [o[0] for o in self.ops], "symbol": self.symbol}
+        if self.bins or self.bouts:
+            record.update(bytes_in=len(self.bins), bytes_out=len(self.bouts))
         # A chain that computes ints is compiled without the SLP vectoriser: at two elements per lane it pairs the limbs of the two elements'
         # redc (they arrive as the halves of one 16-byte load) into vector operations and the kernel of four predicates over P-256 comes to
         # 380 registers instead of 119.  Chains without ints are compiled as they always were
@@ -518,10 +568,13 @@ class FusedChain:
 
     def _split(self, inputs, what: str):
         ch = self.chain
-        if len(inputs) != ch.nin + ch.nshared + ch.nsel:
-            raise ValueError("chain %s takes %d element %s followed by %d shared operands (%d limbs each, on the host) and %d int32 selector arrays"
-                             % (ch.name, ch.nin, what, ch.nshared, ch.params.nlimbs, ch.nsel))
-        return inputs[:ch.nin], [self._limbs(b) for b in inputs[ch.nin:ch.nin + ch.nshared]], inputs[ch.nin + ch.nshared:]
+        nb = len(ch.bins)
+        if len(inputs) != ch.nin + nb + ch.nshared + ch.nsel:
+            raise ValueError("chain %s takes %d element %s%s followed by %d shared operands (%d limbs each, on the host) and %d int32 selector arrays"
+                             % (ch.name, ch.nin, what, ", %d arrays of byte records (uint8 [n, %d])" % (nb, ch.params.nbytes) if nb else "",
+                                ch.nshared, ch.params.nlimbs, ch.nsel))
+        k = ch.nin + nb
+        return inputs[:ch.nin], list(inputs[ch.nin:k]), [self._limbs(b) for b in inputs[k:k + ch.nshared]], inputs[k + ch.nshared:]
 
     def _limbs(self, b):
         """one shared operand as host words of the chain's word length: a sequence of Nlimbs ints or a CPU integer tensor, as Field.modmuls takes b0"""
@@ -537,26 +590,34 @@ class FusedChain:
         return (word * len(b))(*[v & ((1 << ch.wl) - 1) for v in b])          # (signed tensors hold the same words)
 
     def _outs(self, out, n: int, like, fresh):
-        """the arrays of out[]: the element outputs (fresh() each where the caller gives none), then one int32 [n] per int output"""
+        """the arrays of out[]: the element outputs (fresh() each where the caller gives none), then one uint8 [n, Nbytes] per byte output,
+        then one int32 [n] per int output"""
         import torch
         ch = self.chain
-        outs = list(out) if out is not None else [fresh() for _ in ch.outs] + [torch.empty(n, dtype=torch.int32, device=like.device) for _ in ch.pouts]
-        if len(outs) != len(ch.outs) + len(ch.pouts):
-            raise ValueError("chain %s has %d outputs%s" % (ch.name, len(ch.outs), " followed by %d int32 outputs" % len(ch.pouts) if ch.pouts else ""))
+        outs = list(out) if out is not None else ([fresh() for _ in ch.outs] + [torch.empty((n, ch.params.nbytes), dtype=torch.uint8, device=like.device) for _ in ch.bouts]
+                                                  + [torch.empty(n, dtype=torch.int32, device=like.device) for _ in ch.pouts])
+        if len(outs) != len(ch.outs) + len(ch.bouts) + len(ch.pouts):
+            raise ValueError("chain %s has %d outputs%s%s" % (ch.name, len(ch.outs), " followed by %d byte-record outputs" % len(ch.bouts) if ch.bouts else "",
+                                                              " followed by %d int32 outputs" % len(ch.pouts) if ch.pouts else ""))
         return outs
 
-    def _run(self, fn, symbol: str, elems, shared, sels, outs, n: int, *ld, device=None):
+    def _run(self, fn, symbol: str, elems, shared, sels, outs, n: int, *ld, device=None, recs=()):
         """what both entries share: the selector check, the pointer arrays and the call on the current stream of the batches' device.
         The entry point reads the shared operands' limbs before it returns: the host arrays need to live no longer than this call"""
         import torch
         for d in sels:
             if d.dtype != torch.int32 or d.numel() != n or not d.is_cuda or not d.is_contiguous() or (device is not None and d.device != device):
                 raise ValueError("selectors are contiguous int32 device tensors with one 0/1 entry per element")
-        dev = device if device is not None else elems[0].device
-        for d in outs[len(self.chain.outs):]:
+        ch = self.chain
+        dev = device if device is not None else (elems[0] if elems else recs[0]).device
+        k = len(ch.outs) + len(ch.bouts)
+        for r in list(recs) + outs[len(ch.outs):k]:
+            if r.dtype != torch.uint8 or r.dim() != 2 or tuple(r.shape) != (n, ch.params.nbytes) or not r.is_cuda or not r.is_contiguous() or r.device != dev:
+                raise ValueError("byte records are contiguous uint8 tensors [n, %d] on the batches' device" % ch.params.nbytes)
+        for d in outs[k:]:
             if d.dtype != torch.int32 or d.dim() != 1 or d.numel() != n or not d.is_cuda or not d.is_contiguous() or d.device != dev:
                 raise ValueError("int outputs are contiguous int32 tensors of n entries on the batches' device")
-        ptrs = [t.data_ptr() for t in elems] + [ctypes.addressof(b) for b in shared] + [t.data_ptr() for t in sels]
+        ptrs = [t.data_ptr() for t in elems] + [t.data_ptr() for t in recs] + [ctypes.addressof(b) for b in shared] + [t.data_ptr() for t in sels]
         ins = (ctypes.c_void_p * len(ptrs))(*ptrs)
         ous = (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
         with torch.cuda.device(dev):
@@ -569,9 +630,11 @@ class FusedChain:
         import torch
         ch = self.chain
         N = ch.params.nlimbs
+        if ch.bins or ch.bouts:
+            raise ValueError("a chain with byte records has no element-major entry; call %s" % ch.symbol)
         if ch.wl == 32:
             raise ValueError("the element-major entry is not built at word length 32: convert with modarith_amd_w32_aos_to_soa and call %s" % ch.symbol)
-        elems, shared, sels = self._split(inputs, "arrays")
+        elems, _, shared, sels = self._split(inputs, "arrays")
         n = elems[0].shape[0]
         outs = self._outs(out, n, elems[0], lambda: torch.empty_like(elems[0]))
         for t in list(elems) + outs[:len(ch.outs)]:
@@ -585,15 +648,21 @@ class FusedChain:
     def __call__(self, *inputs, out: Optional[Sequence] = None, device=None):
         from .field import Field
         ch = self.chain
-        inputs, shared, sels = self._split(inputs, "batches")
-        dev = device if device is not None else inputs[0].device
+        inputs, recs, shared, sels = self._split(inputs, "batches")
+        dev = device if device is not None else (inputs[0] if inputs else recs[0]).device
         F = self._fields.get(dev)
         if F is None:                                  # binding a Field derives the prime's constants: once per device, not per call
             F = self._fields[dev] = Field(ch.prime, dev, wl=ch.wl)
-        n = F._chk(*inputs)
-        outs = self._outs(out, n, inputs[0], lambda: F._out(inputs[0], None))
-        n = F._chk(*inputs, *outs[:len(ch.outs)])
-        return self._run(self.fn, ch.symbol, inputs, shared, sels, outs, n, F._ld(inputs[0]), device=F.device)
+        if not inputs and ch.outs:                     # element results of byte records alone: batches as the field makes them
+            n = recs[0].shape[0]
+            outs = self._outs(out, n, recs[0], lambda: F.empty(n))
+        else:
+            n = F._chk(*inputs) if inputs else recs[0].shape[0]
+            outs = self._outs(out, n, inputs[0] if inputs else recs[0], lambda: F._out(inputs[0], None))
+        elems = list(inputs) + outs[:len(ch.outs)]
+        if elems and F._chk(*elems) != n:
+            raise ValueError("the element batches hold %d elements, the byte records %d" % (F._chk(*elems), n))
+        return self._run(self.fn, ch.symbol, inputs, shared, sels, outs, n, F._ld(elems[0]) if elems else n, device=F.device, recs=recs)
 
 
 def bench_chain(prime: str = "X25519") -> Chain:
@@ -624,6 +693,23 @@ def oncurve_chain(curve: str = "NIST256", wl: int = 64, name: str = "oncurve"):
     b = ch.shared()
     lhs = ch.modsqr(y)
     ch.output(ch.modcmp(lhs, ch.modadd(ch.modsub(ch.modmul(ch.modsqr(x), x), ch.modmli(x, 3)), b)))
+    return ch, [internal_limbs(c.field, c.b, wl)]
+
+
+def pubkey_chain(curve: str = "NIST256", wl: int = 64, name: str = "pubkey"):
+    """what a batched ECDSA verifier runs before it trusts an uncompressed public key Q = (x, y) as it arrives: two byte-record inputs, the
+    affine coordinates (big-endian, Nbytes each), b shared, ONE int32 per key out:  ok = flag(x) & flag(y) & modcmp(y^2, x^3 - 3x + b)
+    -- both coordinates below p and the point on the curve (a = -3).  64 bytes in and 4 out per P-256 key; oncurve_chain() needs two
+    modimp passes in front of it.  Returns (chain, [limbs of b]); f(xbytes, ybytes, b) -> (ok,)"""
+    from .curves import wcurve
+    c = wcurve(curve)
+    if c.a != -3:
+        raise ValueError("pubkey_chain is written for a = -3 (got %s)" % curve)
+    ch = Chain(c.field, name, wl=wl)
+    (x, fx), (y, fy) = ch.input_bytes(), ch.input_bytes()
+    b = ch.shared()
+    on = ch.modcmp(ch.modsqr(y), ch.modadd(ch.modsub(ch.modmul(ch.modsqr(x), x), ch.modmli(x, 3)), b))
+    ch.output(ch.land(ch.land(fx, fy), on))
     return ch, [internal_limbs(c.field, c.b, wl)]
 
 
@@ -671,10 +757,12 @@ def parse(prime: str, name: str, text: str, wl: int = 64) -> Chain:
     function takes one (modmli, modnsqr, modint); modone() and modzer() take nothing.  Function names are the chain's methods, i.e. field.c's.
     The predicates (modis0, modis1, modsign, modcmp, modqr) give ints; `not d`, `d & e`, `d | e`, `d ^ e` are lnot / land / lor / lxor on
     ints and selectors (0 / 1; `not` binds loosest: write `d & (not e)`); modsqrt(a, h), modinv(a, h), modqr(x, h) take the progenitor as
-    an optional second argument; `out` takes ints as well: int32 results after the element results."""
+    an optional second argument; `out` takes ints as well: int32 results after the element results.
+    `bytes a, b` declares byte-record inputs (a is what modimp leaves), `flag(a)` is modimp's return value for that input, an int like the
+    predicates', and `outbytes expr, ...` outputs modexp of the expressions as byte records."""
     import ast
     ch = Chain(prime, name, wl)
-    env = {}
+    env, flags = {}, {}
     _INT_AST = {ast.BitAnd: "land", ast.BitOr: "lor", ast.BitXor: "lxor"}
 
     def ev(node):
@@ -690,6 +778,10 @@ def parse(prime: str, name: str, text: str, wl: int = 64) -> Chain:
             return ch.lnot(ev(node.operand))
         if isinstance(node, ast.BinOp) and type(node.op) in _INT_AST:
             return getattr(ch, _INT_AST[type(node.op)])(ev(node.left), ev(node.right))
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id == "flag" and not node.keywords:
+            if len(node.args) != 1 or not isinstance(node.args[0], ast.Name) or node.args[0].id not in flags:
+                raise ValueError("flag() takes the name of a byte input: %r" % ast.unparse(node))
+            return flags[node.args[0].id]
         if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and not node.keywords:
             fn = node.func.id
             if fn not in _OPS or not hasattr(ch, fn):
@@ -708,9 +800,15 @@ def parse(prime: str, name: str, text: str, wl: int = 64) -> Chain:
         elif head == "sel":
             for nm in [t.strip() for t in rest.split(",")]:
                 env[nm] = ch.selector()
+        elif head == "bytes":
+            for nm in [t.strip() for t in rest.split(",")]:
+                env[nm], flags[nm] = ch.input_bytes()
         elif head == "out":
             for node in ast.parse("(%s,)" % rest, mode="eval").body.elts:
                 ch.output(ev(node))
+        elif head == "outbytes":
+            for node in ast.parse("(%s,)" % rest, mode="eval").body.elts:
+                ch.output_bytes(ev(node))
         else:
             node = ast.parse(st).body[0]
             if not isinstance(node, ast.Assign) or len(node.targets) != 1:
@@ -745,11 +843,12 @@ def main(argv: List[str]) -> int:
         print(e)
         return 2
     print("%s %s" % ("built" if f.built else "up to date:", f.path))
-    print("int %s(const void *const *in /* %d element batches%s%s */, void *const *out /* %d%s */, size_t n, size_t ld, void *stream);"
-          % (ch.symbol, ch.nin, (", then %d host pointers to shared operands of %d limbs" % (ch.nshared, ch.params.nlimbs)) if ch.nshared else "",
+    recs = lambda k: (", then %d arrays of n records of %d bytes" % (k, ch.params.nbytes)) if k else ""
+    print("int %s(const void *const *in /* %d element batches%s%s%s */, void *const *out /* %d%s */, size_t n, size_t ld, void *stream);"
+          % (ch.symbol, ch.nin, recs(len(ch.bins)), (", then %d host pointers to shared operands of %d limbs" % (ch.nshared, ch.params.nlimbs)) if ch.nshared else "",
              (", then %d int32 selector arrays" % ch.nsel) if ch.nsel else "", len(ch.outs),
-             (" element batches, then %d int32 arrays of n entries" % len(ch.pouts)) if ch.pouts else ""))
-    if ch.wl == 64:
+             ((" element batches" + recs(len(ch.bouts)) + (", then %d int32 arrays of n entries" % len(ch.pouts) if ch.pouts else "")) if ch.pouts or ch.bouts else "")))
+    if ch.wl == 64 and not (ch.bins or ch.bouts):
         print("int %s(const void *const *in, void *const *out, size_t n, void *stream);   /* the same over element-major arrays x[n][Nlimbs] */" % ch.aos_symbol)
     print("HBM bytes per element: %d fused, %d call by call" % (ch.traffic_bytes(), ch.unfused_traffic_bytes()))
     return 0
