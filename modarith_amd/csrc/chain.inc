@@ -18,6 +18,13 @@
 //                                                                         io.imp(j, v, s) per byte input, io.exp(k, v) per byte output
 // and then defines its `extern "C"` symbols over chain_batch() and chain_aos().  Editing this file rebuilds every chain (generate.key_of
 // hashes all of csrc/).
+//
+// THE ARRAYS OF A CALL, in this order (the one statement of it on this side; fuse.Chain.layout() is the same list for the Python side):
+//   in[]   NIN element batches | CHAIN_NBIN arrays of n byte records | CHAIN_NSHARED HOST pointers, Nlimbs words each | NSEL int32 device
+//          arrays, one entry per element
+//   out[]  NOUT element batches | CHAIN_NBOUT arrays of n byte records | CHAIN_NPRED int32 device arrays of n entries
+// (_aos takes the same with element-major arrays for the batches; it has no byte records.)  The constants IN_* / OUT_* below are the first
+// slot of each kind: every entry body goes through them.
 #if MA_WL == 32
 using ma::check_launch;         // (the host helpers of capi_common.h; the 64-bit unit has all of namespace ma in scope)
 using ma::grid_for;
@@ -37,23 +44,24 @@ static_assert(!HEAVY || EPT_CAP == 1, "the long chains run one element per lane"
 #endif
 // Shared operands (CHAIN_NSHARED > 0): one field element each, the same for every element of the batch.  They travel BY VALUE in the
 // kernel arguments, as the Elem<P> of k_mul_shared (kernels.h) does: wave-uniform, so the compiler may keep them and what it derives
-// from them alone in SGPRs.  The entry points read them from HOST memory before they return (in[NIN .. NIN + CHAIN_NSHARED): Nlimbs words
-// each, as modmuls reads b0_host): no device buffer, no copy to order on the stream, and a call under stream capture bakes the value in.
-// Without them Args, the kernels' signatures and the host bodies are what they were.
+// from them alone in SGPRs.  The entry points read them from HOST memory, once, before they return (Nlimbs words each, as modmuls reads
+// b0_host): no device buffer, no copy to order on the stream, and a call under stream capture bakes the value in.  Without them Args and
+// the kernels' signatures are what they were.
 #ifndef CHAIN_NSHARED
 #define CHAIN_NSHARED 0
 #endif
 static_assert(CHAIN_NSHARED >= 0 && CHAIN_NSHARED <= 8, "a chain takes at most 8 shared operands");
 // Int results (CHAIN_NPRED > 0): the ints a chain computes (modis0 / modis1 / modsign / modcmp / modqr and the 0/1 expressions on them) that
-// it declares outputs.  One int32 device array of n contiguous entries each, out[NOUT .. NOUT + CHAIN_NPRED), indexed BY ELEMENT as the
-// selectors are, whatever the layout of the element batches.  A chain may have nothing else to return (NOUT == 0).  An int result may be
-// the array of a selector input: a lane reads its entries (io.sel) before it stores them (io.pred), and no other lane touches them.
+// it declares outputs.  One int32 device array of n contiguous entries each, indexed BY ELEMENT as the selectors are, whatever the layout
+// of the element batches.  A chain may have nothing else to return (NOUT == 0).  An int result may be the array of a selector input: a
+// lane reads its entries (io.sel) before it stores them (io.pred), and no other lane touches them.  Args::pred is a zero-length array
+// without int results: it adds nothing to the kernel arguments.
 #ifndef CHAIN_NPRED
 #define CHAIN_NPRED 0
 #endif
 // Byte records (CHAIN_NBIN + CHAIN_NBOUT > 0): arrays of n big-endian records of P::NBYTES bytes, rec[j * NBYTES + i], what modimp reads and
-// modexp writes; record index = element index.  The kernels and the entry of such a chain are in the section "byte records" below; with
-// both 0 nothing of it is compiled and this file is what it was.
+// modexp writes; record index = element index.  The kernels of such a chain are in the section "byte records" below; with both 0 none of
+// them is compiled, BArgs stays on the host and k_chain is launched as it always was.
 #ifndef CHAIN_NBIN
 #define CHAIN_NBIN 0
 #endif
@@ -62,41 +70,37 @@ static_assert(CHAIN_NSHARED >= 0 && CHAIN_NSHARED <= 8, "a chain takes at most 8
 #endif
 static_assert(CHAIN_NBIN >= 0 && CHAIN_NBOUT >= 0 && NIN + CHAIN_NBIN > 0, "a chain reads at least one array");
 static_assert(CHAIN_NPRED >= 0 && NOUT + CHAIN_NPRED + CHAIN_NBOUT > 0, "a chain returns at least one array");
-#if CHAIN_NPRED > 0
-#define CHAIN_PRED_ARGS int* pred[CHAIN_NPRED];
-#else
-#define CHAIN_PRED_ARGS
-#endif
+#define CHAIN_BYTES (CHAIN_NBIN + CHAIN_NBOUT > 0)
+// the first slot of each kind of array in in[] and out[] (the order: the head of this file); the element batches start at 0
+constexpr int IN_BYTES = NIN, IN_SHARED = IN_BYTES + CHAIN_NBIN, IN_SEL = IN_SHARED + CHAIN_NSHARED;
+constexpr int OUT_BYTES = NOUT, OUT_PRED = OUT_BYTES + CHAIN_NBOUT;
 #if CHAIN_NSHARED > 0
-struct Args { const spint* in[NIN]; spint* out[NOUT > 0 ? NOUT : 1]; const int* sel[NSEL > 0 ? NSEL : 1]; CHAIN_PRED_ARGS Elem<P> sh[CHAIN_NSHARED]; };
+struct Args { const spint* in[NIN]; spint* out[NOUT > 0 ? NOUT : 1]; const int* sel[NSEL > 0 ? NSEL : 1]; int* pred[CHAIN_NPRED]; Elem<P> sh[CHAIN_NSHARED]; };
 MA_DEV const spint* shared_of(const Args& A, int j) { return A.sh[j].l; }
-void shared_from_host(Args& A, const void* const* in) {
-    for (int j = 0; j < CHAIN_NSHARED; j++)
-        for (int i = 0; i < P::N; i++) A.sh[j].l[i] = static_cast<const spint*>(in[NIN + j])[i];
-}
 #else
-struct Args { const spint* in[NIN]; spint* out[NOUT > 0 ? NOUT : 1]; const int* sel[NSEL > 0 ? NSEL : 1]; CHAIN_PRED_ARGS };
+struct Args { const spint* in[NIN]; spint* out[NOUT > 0 ? NOUT : 1]; const int* sel[NSEL > 0 ? NSEL : 1]; int* pred[CHAIN_NPRED]; };
 MA_DEV const spint* shared_of(const Args&, int) { return nullptr; }
-void shared_from_host(Args&, const void* const*) {}
 #endif
+struct BArgs { const unsigned char* bin[CHAIN_NBIN > 0 ? CHAIN_NBIN : 1]; unsigned char* bout[CHAIN_NBOUT > 0 ? CHAIN_NBOUT : 1]; };    // (a kernel argument of the byte-record kernels only)
+constexpr int NB = P::NBYTES;
 
-// ---- limb-interleaved batches: load_soa / store_soa at lane t, EPT consecutive elements
+// ---- limb-interleaved batches: load_soa / store_soa at lane t, EPT consecutive elements.  (The int side -- shared, sel, pred -- is
+// spelt out in each of the three lane I/Os of this file: written once over "the lane's first element" and "is entry E live" it
+// compiled to other code in the kernels of chains with selectors or int results, profiles/chain_one_entry.json)
 template <int EPT> struct SoaIO {
     const Args& A; Ld L; size_t t;
     MA_DEV void load(int i, spint (*v)[P::N]) const { load_soa<P, EPT>(A.in[i], L, t, v); }
     MA_DEV const spint* shared(int j) const { return shared_of(A, j); }
     MA_DEV void sel(int k, int* s) const { static_for<0, EPT>([&](auto E) { s[E] = A.sel[k][(size_t)EPT * t + E]; }); }
     MA_DEV void store(int k, spint (*v)[P::N]) const { store_soa<P, EPT>(A.out[k], L, t, v); }
-#if CHAIN_NPRED > 0
     MA_DEV void pred(int k, const int* s) const { static_for<0, EPT>([&](auto E) { A.pred[k][(size_t)EPT * t + E] = s[E]; }); }   // (one 4-byte store per element: no alignment asked of the array)
-#endif
 };
 template <int EPT>
 __global__ __launch_bounds__(CBLOCK) CHAIN_KERNEL_ATTR void k_chain(Args A, size_t nthreads, Ld L) {
     for (size_t t = (size_t)blockIdx.x * CBLOCK + threadIdx.x; t < nthreads; t += (size_t)gridDim.x * CBLOCK) chain_step<EPT>(SoaIO<EPT>{A, L, t});
 }
 
-#if CHAIN_NBIN + CHAIN_NBOUT > 0
+#if CHAIN_BYTES
 // ---- byte records: modimp at the head of the chain and modexp at its tail, inside the kernel.  io.imp(j, v, s) leaves in v the CANONICAL
 // limbs of the integer that record j spells (limbs_from_words, then modfsb: inside the limb contract, so an imported value joins the
 // vote as any input does) and in s modimp's return value; the chain's body starts with F::nres of it, under the policy the wave voted
@@ -112,8 +116,7 @@ __global__ __launch_bounds__(CBLOCK) CHAIN_KERNEL_ATTR void k_chain(Args A, size
 //            barriers (the CHAIN_AOS_IMAGES rule); the outputs go through the first image.
 // Which of the two a call on aligned arrays takes is BYTES_STAGED below (measured: tools/chain_bytes_rate.py, docs/fused_chains.md);
 // the environment variable MA_CHAIN_BYTES=staged|direct, read at every call, overrides it (tests, the rate tool).
-struct BArgs { const unsigned char* bin[CHAIN_NBIN > 0 ? CHAIN_NBIN : 1]; unsigned char* bout[CHAIN_NBOUT > 0 ? CHAIN_NBOUT : 1]; };
-constexpr int NB = P::NBYTES, NW = Field<P>::NW;
+constexpr int NW = Field<P>::NW;
 constexpr bool BYTES_STAGED = CHAIN_BYTES_STAGED; // the path of a call on 16-byte aligned record arrays: the unit says (fuse.BYTES_IO_DEFAULT)
 MA_DEV int imp_words(const word_t* w, spint* v) {
     Field<P>::limbs_from_words(w, v);
@@ -200,9 +203,7 @@ template <int EPT> struct StagedIO {
     MA_DEV const spint* shared(int j) const { return shared_of(A, j); }
     MA_DEV void sel(int k, int* s) const { static_for<0, EPT>([&](auto E) { s[E] = live() ? A.sel[k][(size_t)EPT * t() + E] : 0; }); }
     MA_DEV void store(int k, spint (*v)[P::N]) const { if (live()) store_soa<P, EPT>(A.out[k], L, t(), v); }
-#if CHAIN_NPRED > 0
     MA_DEV void pred(int k, const int* s) const { static_for<0, EPT>([&](auto E) { if (live()) A.pred[k][(size_t)EPT * t() + E] = s[E]; }); }
-#endif
     MA_DEV void imp(int j, spint (*v)[P::N], int* s) const {
         unsigned char* img = sh;
         if constexpr (images(EPT) == CHAIN_NBIN) {
@@ -244,17 +245,49 @@ __global__ __launch_bounds__(CBLOCK) CHAIN_KERNEL_ATTR void k_chain_staged(Args 
         chain_step<EPT>(StagedIO<EPT>{A, B, L, t0, cnt, sh});
     }
 }
-template <int EPT> void launch_bytes(bool staged, const Args& A, const BArgs& B, size_t nt, Ld L, bool tiled, hipStream_t s) {
-    if constexpr (STAGED_BUILT) if (staged) { k_chain_staged<EPT><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, B, nt, L); return; }
-    k_chain_direct<EPT><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, B, nt, L);
+#endif  // byte records
+
+// ---- the host side of both entries.  A call's arrays as the kernels take them (the shared operands are read from the host here, once);
+// addr / baddr: the OR of the addresses of the element arrays / of the record arrays
+struct Call { Args A; BArgs B; uintptr_t addr = 0, baddr = 0; };
+Call call_of(const void* const* in, void* const* out) {
+    Call c;
+    for (int i = 0; i < NIN; i++) { c.A.in[i] = (const spint*)in[i]; c.addr |= reinterpret_cast<uintptr_t>(in[i]); }
+    for (int i = 0; i < NOUT; i++) { c.A.out[i] = (spint*)out[i]; c.addr |= reinterpret_cast<uintptr_t>(out[i]); }
+    for (int i = 0; i < CHAIN_NBIN; i++) { c.B.bin[i] = (const unsigned char*)in[IN_BYTES + i]; c.baddr |= reinterpret_cast<uintptr_t>(in[IN_BYTES + i]); }
+    for (int i = 0; i < CHAIN_NBOUT; i++) { c.B.bout[i] = (unsigned char*)out[OUT_BYTES + i]; c.baddr |= reinterpret_cast<uintptr_t>(out[OUT_BYTES + i]); }
+    for (int i = 0; i < NSEL; i++) c.A.sel[i] = (const int*)in[IN_SEL + i];
+    for (int i = 0; i < CHAIN_NPRED; i++) c.A.pred[i] = (int*)out[OUT_PRED + i];
+#if CHAIN_NSHARED > 0
+    for (int j = 0; j < CHAIN_NSHARED; j++)
+        for (int i = 0; i < P::N; i++) c.A.sh[j].l[i] = static_cast<const spint*>(in[IN_SHARED + j])[i];
+#endif
+    return c;
+}
+// the same call from element `done` on; o: that element's offset in an element array.  (A copy: the shared operands are those already read)
+Call rest_of(Call c, size_t done, size_t o) {
+    for (int i = 0; i < NIN; i++) c.A.in[i] += o;
+    for (int i = 0; i < NOUT; i++) c.A.out[i] += o;
+    for (int i = 0; i < CHAIN_NBIN; i++) c.B.bin[i] += done * NB;
+    for (int i = 0; i < CHAIN_NBOUT; i++) c.B.bout[i] += done * NB;
+    for (int i = 0; i < NSEL; i++) c.A.sel[i] += done;
+    for (int i = 0; i < CHAIN_NPRED; i++) c.A.pred[i] += done;
+    return c;
+}
+// nt lanes of EPT elements each: k_chain, or with byte records one of their two kernels
+template <int EPT> void launch(bool staged, const Call& c, size_t nt, Ld L, unsigned grid, hipStream_t s) {
+#if CHAIN_BYTES
+    if constexpr (STAGED_BUILT) if (staged) { k_chain_staged<EPT><<<grid, CBLOCK, 0, s>>>(c.A, c.B, nt, L); return; }
+    k_chain_direct<EPT><<<grid, CBLOCK, 0, s>>>(c.A, c.B, nt, L);
+#else
+    k_chain<EPT><<<grid, CBLOCK, 0, s>>>(c.A, nt, L);
+#endif
 }
 
-// in[0 .. NIN): element batches; then CHAIN_NBIN arrays of n byte records; then CHAIN_NSHARED host pointers; then NSEL int32 selector arrays
-// out[0 .. NOUT): element batches; then CHAIN_NBOUT arrays of n byte records; then CHAIN_NPRED int32 arrays of n entries
-// Record arrays are 8-byte aligned where NBYTES is a multiple of 8 (the rule of modimp_<P>_batch) and may be anywhere otherwise; a byte
-// output may be the array of a byte input.  ld is ignored by a chain without element arrays.  (The _batch symbol of a unit with byte
-// records calls this entry, not the one below.)
-int chain_bytes_batch(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) {
+// Element batches are flat (ld >= n) or tiled (ld < n: the tile); without element arrays on either side ld is ignored.  Record arrays are
+// 8-byte aligned where NBYTES is a multiple of 8 (the rule of modimp_<P>_batch) and may be anywhere otherwise; a byte output may be the
+// array of a byte input
+int chain_batch(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) {
     if (n == 0) return 0;
     constexpr bool elems = NIN + NOUT > 0;
     Ld L(elems ? ld : n);
@@ -262,102 +295,33 @@ int chain_bytes_batch(const void* const* in, void* const* out, size_t n, size_t 
         if (ld < 128 || (ld & (ld - 1)) != 0) { set_error(CHAIN_SYMBOL "_batch: a limb stride below n selects the tiled layout and must be a power of two >= 128"); return (int)hipErrorInvalidValue; }
         L = Ld(ld, (unsigned)__builtin_ctzll((unsigned long long)ld));
     }
-    Args A;
-    BArgs B;
-    uintptr_t addr = 0, baddr = 0;
-    for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; addr |= reinterpret_cast<uintptr_t>(in[i]); }
-    for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; addr |= reinterpret_cast<uintptr_t>(out[i]); }
-    for (int i = 0; i < CHAIN_NBIN; i++) { B.bin[i] = (const unsigned char*)in[NIN + i]; baddr |= reinterpret_cast<uintptr_t>(in[NIN + i]); }
-    for (int i = 0; i < CHAIN_NBOUT; i++) { B.bout[i] = (unsigned char*)out[NOUT + i]; baddr |= reinterpret_cast<uintptr_t>(out[NOUT + i]); }
-    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + CHAIN_NBIN + CHAIN_NSHARED + i];
-#if CHAIN_NPRED > 0
-    for (int i = 0; i < CHAIN_NPRED; i++) A.pred[i] = (int*)out[NOUT + CHAIN_NBOUT + i];
-#endif
-    shared_from_host(A, in + CHAIN_NBIN);
-    if (NB % 8 == 0 && (baddr & 7u)) { set_error(CHAIN_SYMBOL "_batch: byte records must be 8-byte aligned"); return (int)hipErrorInvalidValue; }
-    bool staged = BYTES_STAGED;
+    const Call c = call_of(in, out);
+    bool staged = false;
+#if CHAIN_BYTES
+    if (NB % 8 == 0 && (c.baddr & 7u)) { set_error(CHAIN_SYMBOL "_batch: byte records must be 8-byte aligned"); return (int)hipErrorInvalidValue; }
+    staged = BYTES_STAGED;
     if (const char* v = getenv("MA_CHAIN_BYTES")) {
         const std::string m(v);
         if (m == "staged") staged = true;
         else if (m == "direct") staged = false;
         else { set_error(CHAIN_SYMBOL "_batch: MA_CHAIN_BYTES is staged or direct"); return (int)hipErrorInvalidValue; }
     }
-    staged = staged && (baddr & 15u) == 0;
-    hipStream_t s = (hipStream_t)stream;
-    const bool tiled = L.s != 63;
-    // elements per lane: the rules of the entry without byte records, on the element arrays (a record array asks nothing of the width)
-    size_t e = EPT_CAP;
-    while (e > 1 && !(n >= e && (!elems || ld % e == 0) && (addr & (e * sizeof(spint) - 1)) == 0)) e /= 2;
-    const size_t nt = n / e, done = nt * e;
-    if constexpr (EPT_BUILT >= 4) if (e == 4) launch_bytes<4>(staged, A, B, nt, L, tiled, s);
-    if constexpr (EPT_BUILT >= 2) if (e == 2) launch_bytes<2>(staged, A, B, nt, L, tiled, s);
-    if (e == 1) launch_bytes<1>(staged, A, B, nt, L, tiled, s);
-    if (done < n) {                                   // fewer than e elements, at records that need not be 16-byte aligned: direct
-        const size_t o = L.off<P::N>(done);
-        Args A2 = A;
-        BArgs B2;
-        for (int i = 0; i < NIN; i++) A2.in[i] = A.in[i] + o;
-        for (int i = 0; i < NOUT; i++) A2.out[i] = A.out[i] + o;
-        for (int i = 0; i < NSEL; i++) A2.sel[i] = A.sel[i] + done;
-#if CHAIN_NPRED > 0
-        for (int i = 0; i < CHAIN_NPRED; i++) A2.pred[i] = A.pred[i] + done;
+    staged = staged && (c.baddr & 15u) == 0;
 #endif
-        for (int i = 0; i < CHAIN_NBIN; i++) B2.bin[i] = B.bin[i] + done * NB;
-        for (int i = 0; i < CHAIN_NBOUT; i++) B2.bout[i] = B.bout[i] + done * NB;
-        k_chain_direct<1><<<1, CBLOCK, 0, s>>>(A2, B2, n - done, Ld(L.ld));
-    }
+    hipStream_t s = (hipStream_t)stream;
+    // elements per lane (the rules of the library's pick_ept, capi_field.inc, on the element arrays: a record array asks nothing of the
+    // width): e elements need n >= e, a stride that is a multiple of e and rows aligned to e words; what is left over (fewer than e
+    // elements) runs one element per lane at its own address, flat stride, records read and written directly
+    size_t e = EPT_CAP;
+    while (e > 1 && !(n >= e && (!elems || ld % e == 0) && (c.addr & (e * sizeof(spint) - 1)) == 0)) e /= 2;
+    const size_t nt = n / e, done = nt * e;
+    const unsigned grid = grid_for(nt, CBLOCK, L.s != 63);
+    if constexpr (EPT_BUILT >= 4) if (e == 4) launch<4>(staged, c, nt, L, grid, s);
+    if constexpr (EPT_BUILT >= 2) if (e == 2) launch<2>(staged, c, nt, L, grid, s);
+    if (e == 1) launch<1>(staged, c, nt, L, grid, s);
+    if (done < n) launch<1>(false, rest_of(c, done, L.off<P::N>(done)), n - done, Ld(L.ld), 1, s);
     return check_launch(CHAIN_SYMBOL "_batch");
 }
-#if MA_WL == 64
-int chain_aos(const void* const*, void* const*, size_t, void*) {        // byte records have no layout: _batch is the entry
-    set_error(CHAIN_SYMBOL "_aos: a chain with byte records has no element-major entry; call " CHAIN_SYMBOL "_batch");
-    return (int)hipErrorInvalidValue;
-}
-#endif
-#else
-// in[0 .. NIN): element batches; then CHAIN_NSHARED host pointers, one per shared operand; then NSEL int32 selector arrays, one entry per element
-// out[0 .. NOUT): element batches; then CHAIN_NPRED int32 arrays of n entries
-int chain_batch(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) {
-    if (n == 0) return 0;
-    Ld L(ld);
-    if (ld < n) {
-        if (ld < 128 || (ld & (ld - 1)) != 0) { set_error(CHAIN_SYMBOL "_batch: a limb stride below n selects the tiled layout and must be a power of two >= 128"); return (int)hipErrorInvalidValue; }
-        L = Ld(ld, (unsigned)__builtin_ctzll((unsigned long long)ld));
-    }
-    Args A;
-    uintptr_t addr = 0;
-    for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; addr |= reinterpret_cast<uintptr_t>(in[i]); }
-    for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; addr |= reinterpret_cast<uintptr_t>(out[i]); }
-    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + CHAIN_NSHARED + i];
-#if CHAIN_NPRED > 0
-    for (int i = 0; i < CHAIN_NPRED; i++) A.pred[i] = (int*)out[NOUT + i];
-#endif
-    shared_from_host(A, in);
-    hipStream_t s = (hipStream_t)stream;
-    const bool tiled = L.s != 63;
-    // elements per lane (the rules of the library's pick_ept, capi_field.inc): e elements need n >= e, a stride that is a multiple of e
-    // and rows aligned to e words; what is left over (fewer than e elements) runs one element per lane at its own address, flat stride
-    size_t e = EPT_CAP;
-    while (e > 1 && !(n >= e && ld % e == 0 && (addr & (e * sizeof(spint) - 1)) == 0)) e /= 2;
-    const size_t nt = n / e, done = nt * e;
-    if constexpr (EPT_BUILT >= 4) if (e == 4) k_chain<4><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, nt, L);
-    if constexpr (EPT_BUILT >= 2) if (e == 2) k_chain<2><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, nt, L);
-    if (e == 1) k_chain<1><<<grid_for(nt, CBLOCK, tiled), CBLOCK, 0, s>>>(A, nt, L);
-    if (done < n) {
-        const size_t o = L.off<P::N>(done);
-        Args B;
-        for (int i = 0; i < NIN; i++) B.in[i] = A.in[i] + o;
-        for (int i = 0; i < NOUT; i++) B.out[i] = A.out[i] + o;
-        for (int i = 0; i < NSEL; i++) B.sel[i] = A.sel[i] + done;
-#if CHAIN_NPRED > 0
-        for (int i = 0; i < CHAIN_NPRED; i++) B.pred[i] = A.pred[i] + done;
-#endif
-        shared_from_host(B, in);                      // (the remainder launch runs on the same shared operands)
-        k_chain<1><<<1, CBLOCK, 0, s>>>(B, n - done, Ld(L.ld));
-    }
-    return check_launch(CHAIN_SYMBOL "_batch");
-}
-#endif  // no byte records
 
 #if defined(CHAIN_AOS_IMAGES) && CHAIN_AOS_IMAGES > 0
 // ---- element-major I/O: x[n][N] in, x[n][N] out (how the scalar callers of field.c hold their elements).  A workgroup of 256 lanes
@@ -438,13 +402,11 @@ struct AosIO {                                        // two elements per lane: 
         static_for<0, 2>([&](auto E) { s[E] = (2 * (size_t)t + E < cnt) ? d[2 * (size_t)t + E] : 0; });
     }
     MA_DEV void store(int k, spint (*v)[P::N]) const { aos_out(A.out[k] + off, cnt, sh, v); }
-#if CHAIN_NPRED > 0
     MA_DEV void pred(int k, const int* s) const {
         const int t = threadIdx.x;
         int* d = A.pred[k] + c0;
         static_for<0, 2>([&](auto E) { if (2 * (size_t)t + E < cnt) d[2 * (size_t)t + E] = s[E]; });
     }
-#endif
 };
 __global__ __launch_bounds__(BLOCK) void k_chain_aos(Args A, size_t n) {
     __shared__ spint sh[CHAIN_AOS_IMAGES * CH * SP];
@@ -459,28 +421,20 @@ __global__ __launch_bounds__(BLOCK) void k_chain_aos(Args A, size_t n) {
     }
 }
 
-// element-major arrays spint x[n][Nlimbs] (16-byte aligned); in[NIN ..): shared operands (host) and int32 selector arrays as in the _batch form;
-// out[NOUT ..): the int32 results, n entries each (no alignment asked of them)
+// element-major arrays spint x[n][Nlimbs], 16-byte aligned; nothing is asked of the int32 arrays
 int chain_aos(const void* const* in, void* const* out, size_t n, void* stream) {
     if (n == 0) return 0;
-    Args A;
-    bool al = true;
-    for (int i = 0; i < NIN; i++) { A.in[i] = (const spint*)in[i]; al = al && aligned16(in[i]); }
-    for (int i = 0; i < NOUT; i++) { A.out[i] = (spint*)out[i]; al = al && aligned16(out[i]); }
-    for (int i = 0; i < NSEL; i++) A.sel[i] = (const int*)in[NIN + CHAIN_NSHARED + i];
-#if CHAIN_NPRED > 0
-    for (int i = 0; i < CHAIN_NPRED; i++) A.pred[i] = (int*)out[NOUT + i];
-#endif
-    shared_from_host(A, in);
-    if (!al) { set_error(CHAIN_SYMBOL "_aos: element-major arrays must be 16-byte aligned"); return (int)hipErrorInvalidValue; }
+    const Call c = call_of(in, out);
+    if (c.addr & 15u) { set_error(CHAIN_SYMBOL "_aos: element-major arrays must be 16-byte aligned"); return (int)hipErrorInvalidValue; }
     const size_t chunks = (n + CH - 1) / CH;
     const size_t cap = (size_t)max_blocks_tiled();
-    k_chain_aos<<<(unsigned)(chunks < cap ? chunks : cap), BLOCK, 0, (hipStream_t)stream>>>(A, n);
+    k_chain_aos<<<(unsigned)(chunks < cap ? chunks : cap), BLOCK, 0, (hipStream_t)stream>>>(c.A, n);
     return check_launch(CHAIN_SYMBOL "_aos");
 }
-#elif defined(CHAIN_AOS_IMAGES)
-int chain_aos(const void* const*, void* const*, size_t, void*) {        // more than 14 limbs: no kernel
-    set_error(CHAIN_SYMBOL "_aos: element-major I/O is built for fields of up to 14 limbs; convert with modarith_amd_aos_to_soa");
+#elif MA_WL == 64
+int chain_aos(const void* const*, void* const*, size_t, void*) {        // no kernel: byte records have no layout, more than 14 limbs no image
+    set_error(CHAIN_BYTES ? CHAIN_SYMBOL "_aos: a chain with byte records has no element-major entry; call " CHAIN_SYMBOL "_batch"
+                          : CHAIN_SYMBOL "_aos: element-major I/O is built for fields of up to 14 limbs; convert with modarith_amd_aos_to_soa");
     return (int)hipErrorInvalidValue;
 }
 #endif

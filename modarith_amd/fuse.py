@@ -24,8 +24,9 @@ the exact ones.  C-ABI of the built plug-in (modarith_amd/plugins/libmodarith_am
     int chain_<name>_<TAG>_batch(const void *const *in, void *const *out, size_t n, size_t ld, void *stream);
     int chain_<name>_<TAG>_aos(const void *const *in, void *const *out, size_t n, void *stream);     /* element-major x[n][Nlimbs] */
 
-(`in`: the element batches, then one HOST pointer per shared operand, then one int32 array per selector of modcmv / modcsw;
-`out`: the element batches, then one int32 array per int output.)
+The order of the arrays in `in` and `out` is stated once on each side: `Chain.layout()` below for Python (the Python call takes and
+returns the arrays in that order; every check, the metadata record and the printed prototype derive from it), the header comment of
+csrc/chain.inc for the entry points; docs/fused_chains.md points to both.
 `ch.shared()` is an operand that is the same for every element of the batch -- a curve's d, a base point's coordinate, a blinding factor:
 Nlimbs words on the host, read by the entry point before it returns and passed by value in the kernel arguments (wave-uniform: scalar
 registers, no array to stream; a call under stream capture bakes the value in), at most 8 a chain; `ch.modint(k)`, `ch.modone()`, `ch.modzer()`
@@ -38,18 +39,16 @@ Field<P>'s functions of those names and return a `Pred`, an int computed inside 
 `ch.lxor(d, e)` are the reference's own `1 - d`, `d & e`, `d | e`, `d ^ e` on predicates and selectors -- defined for operands that are 0 or 1,
 as they are there; `modcmv` / `modcsw` take a `Pred` where they take a selector (still lane predication: no branch, no `?:`, no loop on a
 computed int); `ch.modsqrt(a, h)`, `ch.modinv(a, h)`, `ch.modqr(x, h)` pass the progenitor `h = ch.modpro(a)` where they pass NULL otherwise;
-and `ch.output(p)` of a `Pred` is an int32 result of one entry per element.  `out` of both entries is then the element arrays followed by
-the int32 arrays (n contiguous entries each, indexed by element for flat and tiled batches alike, no alignment asked; one may be the array
-of a selector input: a lane reads its entries before it stores), and a chain may have no other output: `oncurve_chain()` below reads two
-coordinate arrays and writes 4 bytes per element, `decompress_chain()` is edwards.c:290-334 as one kernel.
+and `ch.output(p)` of a `Pred` is an int32 result of one entry per element (n contiguous entries, indexed by element for flat and tiled
+batches alike, no alignment asked; it may be the array of a selector input: a lane reads its entries before it stores), and a chain may
+have no other output: `oncurve_chain()` below reads two coordinate arrays and writes 4 bytes per element, `decompress_chain()` is
+edwards.c:290-334 as one kernel.
 
 A chain can speak bytes: `v, ok = ch.input_bytes()` is a byte-record input -- uint8 [n, Nbytes], big-endian, the layout of modimp_<P>_batch --
 with v what Field.modimp leaves (the integer the bytes spell, modfsb, nres) and ok its return value as a `Pred` (1 where the integer was
 below p); `ch.output_bytes(v)` is a byte-record output, modexp(v).  modimp and modexp then run inside the kernel: `c = a * b` on wire values
-moves 96 bytes an element over X25519 where the four calls move 344.  `in`: the element batches, then the record arrays, then the shared
-host pointers, then the selector arrays; `out`: the element arrays, then the record arrays, then the int32 arrays; the Python call takes
-and returns them in that order.  Records are 8-byte aligned where Nbytes is a multiple of 8 (the rule of modimp_<P>_batch) and may be
-anywhere otherwise; a byte output may be the array of a byte input.  A chain needs at least one element batch or one byte input: without
+moves 96 bytes an element over X25519 where the four calls move 344.  Records are 8-byte aligned where Nbytes is a multiple of 8 (the
+rule of modimp_<P>_batch) and may be anywhere otherwise; a byte output may be the array of a byte input.  A chain needs at least one element batch or one byte input: without
 element arrays on either side `ld` is ignored.  There is no element-major entry for such a chain (`_aos` refuses).  `pubkey_chain()` below
 checks an uncompressed P-256 public key as it arrives, 64 bytes in and 4 out.  Out of scope: little-endian records (the RFC 7748 / RFC 8032
 wire formats: the reference reverses them on the host), taking a sign bit out of a record, modshl / modshr / mod2r.  docs/fused_chains.md,
@@ -70,7 +69,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from typing import List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 from . import _lib, emit
 from . import generate as _gen
@@ -84,7 +83,15 @@ _OPS = {"modmul": 2, "modadd": 2, "modsub": 2, "modsqr": 1, "modneg": 1, "nres":
         "modis0": 1, "modis1": 1, "modsign": 1, "modcmp": 2, "modqr": 1, "lnot": 0, "land": 0, "lor": 0, "lxor": 0}
 _HEAVY = ("modinv", "modpro", "modsqrt", "modqr")  # long exponentiation chains: one element per lane
 _PREDS = ("modis0", "modis1", "modsign", "modcmp", "modqr")      # Field<P> functions that return an int: the result is a Pred
-_INT_OPS = {"lnot": "1 - s%d", "land": "s%d & s%d", "lor": "s%d | s%d", "lxor": "s%d ^ s%d"}     # the plain C the reference writes on its 0/1 ints
+_INT_OPS = ("lnot", "land", "lor", "lxor")        # the plain C the reference writes on its 0/1 ints
+# an operation as a line of body<F>, over the fields of its Op (h: the progenitor b, or nullptr); the rest: F::op(operands, result), by operand count
+_CALLS = {"modcsw": "F::modcpy(v{a}, v{dst}); F::modcpy(v{b}, v{dst2}); F::modcsw(s{sa}, v{dst}, v{dst2});",
+          "modcmv": "F::modcpy(v{b}, v{dst}); F::modcmv(s{sa}, v{a}, v{dst});",
+          "modnsqr": "F::modcpy(v{a}, v{dst}); F::modnsqr(v{dst}, {imm});", "modhaf": "F::modcpy(v{a}, v{dst}); F::modhaf(v{dst});",
+          "modsqrt": "F::modsqrt(v{a}, {h}, v{dst});", "modinv": "F::modinv(v{a}, {h}, v{dst}); inv_normalise<F>(v{dst});",
+          "modqr": "s{dst} = F::modqr({h}, v{a});", "modmli": "F::modmli(v{a}, {imm}, v{dst});", "modint": "F::modint({imm}, v{dst});",
+          "lnot": "s{dst} = 1 - s{sa};", "land": "s{dst} = s{sa} & s{sb};", "lor": "s{dst} = s{sa} | s{sb};", "lxor": "s{dst} = s{sa} ^ s{sb};",
+          0: "F::{op}(v{dst});", 1: "F::{op}(v{a}, v{dst});", 2: "F::{op}(v{a}, v{b}, v{dst});"}
 _WITH_H = ("modinv", "modsqrt", "modqr")          # take an optional progenitor h = modpro(a)
 _LAZY = ("modadd_lazy", "modsub_lazy", "modneg_lazy")
 MAX_OPS = 256
@@ -122,6 +129,18 @@ class Pred:
         self.chain, self.idx = chain, idx
 
 
+class Op(NamedTuple):
+    """one operation of a chain.  Element values and ints are two index spaces (v<k> and s<k> in the emitted text); -1 = no such operand"""
+    op: str
+    dst: int                # what it defines: a value, or for the predicates and the int expressions an int
+    a: int = -1             # element operands; b of modinv / modsqrt / modqr is the optional progenitor
+    b: int = -1
+    sa: int = -1            # int operands: of lnot / land / lor / lxor, and sa the selector of modcmv / modcsw
+    sb: int = -1
+    imm: int = 0            # the C int of modmli / modint / modnsqr
+    dst2: int = -1          # modcsw: the second value it defines
+
+
 class Chain:
     def __init__(self, prime: str, name: str, wl: int = 64):
         if not _NAME_RE.match(name):
@@ -142,7 +161,7 @@ class Chain:
         self.sh_idx: List[int] = []         # the values that are shared operands (one element for the whole batch), in the order of in[]
         self.nsel = 0                       # per-element int selectors (modcmv / modcsw): int32 arrays after the element inputs
         self.lazy = set()                   # values produced by a generic=False operation
-        self.ops: List[tuple] = []          # (op, dst, a, b, imm)
+        self.ops: List[Op] = []
         self.outs: List[int] = []
         self.npred = 0                      # ints computed inside the chain (Pred): s<nsel> .. s<nsel + npred - 1>
         self.pouts: List[int] = []          # the ints that are outputs (indices of the int space), in the order of out[] after the element outputs
@@ -156,18 +175,33 @@ class Chain:
         self.nvals += 1
         return v
 
-    def input(self) -> Val:
+    def _declaring(self) -> None:                     # every kind of input: the ints' places (selectors first) and the vote rest on it
         if self.ops:
             raise ValueError("declare every input before the first operation")
+
+    def _room(self) -> None:                          # every operation
+        if len(self.ops) >= MAX_OPS:
+            raise ValueError("chains are limited to %d operations" % MAX_OPS)
+
+    def layout(self) -> Tuple[Dict[str, int], Dict[str, int]]:
+        """THE ARRAYS OF A CALL: (in, out), each the kinds of array in the order they are passed, with how many of the kind.  The one statement
+        of that order on the Python side -- FusedChain's argument checks, the metadata record and prototype() derive from it -- and the
+        same list as the header comment of csrc/chain.inc, whose entry points take them as `in[]` and `out[]`.
+        in:  element batches, byte-record arrays (uint8 [n, Nbytes]), shared operands (HOST: Nlimbs words each), int32 selector arrays;
+        out: element batches, byte-record arrays, int32 arrays of n entries"""
+        return ({"elements": self.nin, "bytes": len(self.bins), "shared": self.nshared, "selectors": self.nsel},
+                {"elements": len(self.outs), "bytes": len(self.bouts), "ints": len(self.pouts)})
+
+    def input(self) -> Val:
+        self._declaring()
         self.nin += 1
         v = self._new()
         self.in_idx.append(v.idx)
         return v
 
     def shared(self) -> Val:
-        """an element operand that is the same for every element of the batch: Nlimbs words on the host, passed after the element batches"""
-        if self.ops:
-            raise ValueError("declare every input before the first operation")
+        """an element operand that is the same for every element of the batch: Nlimbs words on the host"""
+        self._declaring()
         if len(self.sh_idx) >= MAX_SHARED:
             raise ValueError("a chain takes at most %d shared operands" % MAX_SHARED)
         v = self._new()
@@ -179,17 +213,16 @@ class Chain:
         return len(self.sh_idx)
 
     def input_bytes(self):
-        """a byte-record input: n records of Nbytes big-endian bytes, after the element batches in in[].  Returns (v, ok): v is what
+        """a byte-record input: n records of Nbytes big-endian bytes.  Returns (v, ok): v is what
         Field.modimp leaves (the integer the bytes spell, modfsb, nres), ok its return value as a Pred: 1 where the integer was below p"""
-        if self.ops:
-            raise ValueError("declare every input before the first operation")
+        self._declaring()
         v, ok = self._new(), Pred(self, self.npred)
         self.npred += 1
         self.bins.append((v.idx, ok.idx))
         return v, ok
 
     def output_bytes(self, v: Val) -> None:
-        """a byte-record output, modexp(v): redc, then Nbytes big-endian bytes a record, after the element outputs in out[]"""
+        """a byte-record output, modexp(v): redc, then Nbytes big-endian bytes a record"""
         self._own(v)
         if v.idx in self.sh_idx:
             raise ValueError("a shared operand is not a per-element array: output_bytes modcpy() of it")
@@ -205,12 +238,12 @@ class Chain:
             if not isinstance(v, Val) or v.chain is not self:
                 raise ValueError("operands must be values of this chain")
 
-    def _op(self, op: str, a: Optional[Val], b: Optional[Val] = None, imm: int = 0) -> Val:
+    def _op(self, op: str, a: Optional[Val], b: Optional[Val] = None, **fields) -> Val:
+        """an operation on element values that defines one; fields: its immediate or its selector"""
         self._own(*[v for v in (a, b) if v is not None])
-        if len(self.ops) >= MAX_OPS:
-            raise ValueError("chains are limited to %d operations" % MAX_OPS)
+        self._room()
         d = self._new()
-        self.ops.append((op, d.idx, a.idx if a is not None else -1, b.idx if b is not None else -1, int(imm)))
+        self.ops.append(Op(op, d.idx, a.idx if a is not None else -1, b.idx if b is not None else -1, **fields))
         return d
 
     def modmul(self, a, b): return self._op("modmul", a, b)
@@ -226,7 +259,7 @@ class Chain:
     def modmli(self, a, k: int):
         if not -(1 << 31) <= int(k) < (1 << 31):
             raise ValueError("modmli takes a C int")
-        return self._op("modmli", a, imm=k)
+        return self._op("modmli", a, imm=int(k))
 
     # the field's constants, as Field<P>::modint / modone / modzer make them (Montgomery form included): no operand
     def modint(self, k: int):
@@ -260,12 +293,11 @@ class Chain:
     def modnsqr(self, a, k: int):
         if not 0 <= int(k) <= 100000:
             raise ValueError("modnsqr count out of range")
-        return self._op("modnsqr", a, imm=k)
+        return self._op("modnsqr", a, imm=int(k))
 
     def selector(self) -> "Sel":
-        """a per-element int input (0 / 1), as the `int b` of modcmv / modcsw: an int32 array, passed after the element inputs"""
-        if self.ops:
-            raise ValueError("declare every input before the first operation")
+        """a per-element int input (0 / 1), as the `int b` of modcmv / modcsw: an int32 array"""
+        self._declaring()
         self.nsel += 1
         return Sel(self, self.nsel - 1)
 
@@ -275,17 +307,16 @@ class Chain:
         return d.idx if isinstance(d, Sel) else self.nsel + d.idx
 
     # ints computed inside the chain.  A Pred's place in the int space is nsel + its own count: selectors are declared before the first operation
-    def _pred(self, op: str, a: int = -1, b: int = -1) -> Pred:
-        if len(self.ops) >= MAX_OPS:
-            raise ValueError("chains are limited to %d operations" % MAX_OPS)
+    def _pred(self, op: str, **operands) -> Pred:
+        self._room()
         d = Pred(self, self.npred)
         self.npred += 1
-        self.ops.append((op, self.nsel + d.idx, a, b, 0))
+        self.ops.append(Op(op, self.nsel + d.idx, **operands))
         return d
 
     def _test(self, op: str, a: Val, b: Optional[Val] = None) -> Pred:
         self._own(*[v for v in (a, b) if v is not None])
-        return self._pred(op, a.idx, b.idx if b is not None else -1)
+        return self._pred(op, a=a.idx, b=b.idx if b is not None else -1)
 
     def modis0(self, a): return self._test("modis0", a)
     def modis1(self, a): return self._test("modis1", a)
@@ -301,27 +332,28 @@ class Chain:
         for d in ds:
             if not isinstance(d, (Sel, Pred)):
                 raise ValueError("int expressions take predicates and selectors, not element values")
-        return [self._sel(d) for d in ds]
+        return dict(zip(("sa", "sb"), (self._sel(d) for d in ds)))
 
-    def lnot(self, d): return self._pred("lnot", *self._ints(d))
-    def land(self, d, e): return self._pred("land", *self._ints(d, e))
-    def lor(self, d, e): return self._pred("lor", *self._ints(d, e))
-    def lxor(self, d, e): return self._pred("lxor", *self._ints(d, e))
+    def lnot(self, d): return self._pred("lnot", **self._ints(d))
+    def land(self, d, e): return self._pred("land", **self._ints(d, e))
+    def lor(self, d, e): return self._pred("lor", **self._ints(d, e))
+    def lxor(self, d, e): return self._pred("lxor", **self._ints(d, e))
 
     def modcmv(self, d, g, f):
         """f' = d ? g : f  (constant time: lane-predicated selects, pseudo.py:1017-1048)"""
-        return self._op("modcmv", g, f, imm=self._sel(d))
+        return self._op("modcmv", g, f, sa=self._sel(d))
 
     def modcsw(self, d, g, f):
         """(g', f') = d ? (f, g) : (g, f)  (pseudo.py:979-1014)"""
         k = self._sel(d)
         self._own(g, f)
+        self._room()
         g2, f2 = self._new(), self._new()
-        self.ops.append(("modcsw", g2.idx, g.idx, f.idx, k, f2.idx))
+        self.ops.append(Op("modcsw", g2.idx, g.idx, f.idx, sa=k, dst2=f2.idx))
         return g2, f2
 
     def output(self, v) -> None:
-        """an element value: a limb array like the inputs; a Pred: an int32 array of one entry per element, after the element outputs in out[]"""
+        """an element value: a limb array like the inputs; a Pred: an int32 array of one entry per element"""
         if isinstance(v, Sel):
             raise ValueError("a selector is the caller's own array: there is nothing to output")
         if isinstance(v, Pred):
@@ -335,10 +367,11 @@ class Chain:
         self.outs.append(v.idx)
 
     # ------------------------------------------------------------------ emission
+    def _long(self) -> bool:                          # an inversion, a progenitor or a square root in the chain: one element per lane
+        return any(o.op in _HEAVY for o in self.ops)
+
     def default_ept(self) -> int:
-        if any(o[0] in _HEAVY for o in self.ops):
-            return 1
-        return 2 if self.wl == 64 else W32_EPT_DEFAULT
+        return 1 if self._long() else 2 if self.wl == 64 else W32_EPT_DEFAULT
 
     @property
     def _tag(self) -> str:
@@ -362,10 +395,10 @@ class Chain:
         w = (self.wl // 8) * self.params.nlimbs
         total = len(self.bins) * (self.params.nbytes + w + 4) + len(self.bouts) * (w + self.params.nbytes)
         for o in self.ops:
-            op = o[0]
+            op = o.op
             if op in _INT_OPS:
                 continue
-            arrays = _OPS[op] + (1 if op in _WITH_H and o[3] >= 0 else 0)
+            arrays = _OPS[op] + (1 if op in _WITH_H and o.b >= 0 else 0)
             if op in _PREDS:
                 total += w * arrays + 4
             else:
@@ -375,10 +408,9 @@ class Chain:
     def _body_lines(self) -> List[str]:
         """the chain as Field<P> calls on registers, one line per operation"""
         L = ["    F::nres(v%d, v%d);" % (i, i) for i, _ in self.bins]      # io.imp() left the canonical limbs: the rest of modimp, on the voted products
-        h_of = lambda h: "nullptr" if h < 0 else "v%d" % h
         tested = set()                                        # values a predicate has read
         for o in self.ops:
-            op, d, a, b, imm = o[:5]
+            op, d, a, b = o.op, o.dst, o.a, o.b
             if op in _PREDS and op != "modqr":
                 # Every predicate starts with redc of its operands.  A second one on the same value would share the pure part of that
                 # redc with the first (the products; the pinned accumulations are not shareable) and keep every partial product live
@@ -393,49 +425,17 @@ class Chain:
                         ab[k] = "v%d" % x
                 L.append("    %ss%d = F::%s(%s);" % (pre, d, op, ", ".join(x for x in ab if x != -1)))
                 continue
-            if op == "modcsw":
-                L.append("    F::modcpy(v%d, v%d); F::modcpy(v%d, v%d); F::modcsw(s%d, v%d, v%d);" % (a, d, b, o[5], imm, d, o[5]))
-            elif op == "modcmv":
-                L.append("    F::modcpy(v%d, v%d); F::modcmv(s%d, v%d, v%d);" % (b, d, imm, a, d))
-            elif op == "modnsqr":
-                L.append("    F::modcpy(v%d, v%d); F::modnsqr(v%d, %d);" % (a, d, d, imm))
-            elif op == "modhaf":
-                L.append("    F::modcpy(v%d, v%d); F::modhaf(v%d);" % (a, d, d))
-            elif op == "modsqrt":
-                L.append("    F::modsqrt(v%d, %s, v%d);" % (a, h_of(b), d))
-            elif op == "modinv":
-                L.append("    F::modinv(v%d, %s, v%d); inv_normalise<F>(v%d);" % (a, h_of(b), d, d))
-            elif op == "modqr":
-                L.append("    s%d = F::modqr(%s, v%d);" % (d, h_of(b), a))
-            elif op in _INT_OPS:
-                L.append("    s%d = %s;" % (d, _INT_OPS[op] % ((a,) if b < 0 else (a, b))))
-            elif op == "modmli":
-                L.append("    F::modmli(v%d, %d, v%d);" % (a, imm, d))
-            elif op == "modint":
-                L.append("    F::modint(%d, v%d);" % (imm, d))
-            elif _OPS[op] == 0:
-                L.append("    F::%s(v%d);" % (op, d))
-            elif _OPS[op] == 2:
-                L.append("    F::%s(v%d, v%d, v%d);" % (op, a, b, d))
-            else:
-                L.append("    F::%s(v%d, v%d);" % (op, a, d))
+            L.append("    " + _CALLS.get(op, _CALLS[_OPS[op]]).format(h="nullptr" if b < 0 else "v%d" % b, **o._asdict()))
         return L + ["    F::redc(v%d, v%d);" % (a, d) for a, d in self.bouts]            # the first half of modexp; io.exp() makes the bytes
 
-    def source(self, ept: Optional[int] = None, policy: str = "vote", waves: int = 0, block: Optional[int] = None) -> str:
-        """The unit: what depends on the chain -- constants, body<F> and chain_step<EPT, IO> -- around csrc/chain.inc, which holds the
-        kernels (k_chain<EPT>, k_chain_aos) and the bodies of the entry points for both word lengths.
-        ept: elements per lane on aligned batches (2 = 16-byte accesses, 1 = 8-byte; at word length 32: 4 / 2 / 1 = 16 / 8 / 4 bytes);
-        None = the measured default.  block: workgroup size, word length 32 only"""
-        if not (self.nin or self.bins) or not (self.outs or self.pouts or self.bouts):
-            raise ValueError("a chain needs at least one input and one output")
-        nbytes = len(self.bins) + len(self.bouts)
-        P, nv, N, w32 = self.prime, self.nvals, self.params.nlimbs, self.wl == 32
-        consts = set(self.in_idx) | set(self.sh_idx)      # what the body only reads: the element inputs and the shared operands
-        shared = set(self.sh_idx)                         # one element for the whole batch: a pointer into the kernel arguments, not a per-lane array
-        if w32:
+    # The unit, piece by piece; every helper returns lines, source() puts them in order
+    def _shape(self, ept, policy, block):
+        """what depends on the word length: (the includes and the namespace, the constants of the build's shape, HEAVY)"""
+        P, N = self.prime, self.params.nlimbs
+        if self.wl == 32:
             if policy != "vote":
                 raise ValueError("word length 32 has one product policy: there is nothing to force")
-            heavy = any(o[0] in _HEAVY for o in self.ops)
+            heavy = self._long()
             cap = 1 if heavy else (ept or self.default_ept())
             if cap not in (1, 2, 4):
                 raise ValueError("elements per lane at word length 32: 1, 2 or 4")
@@ -446,78 +446,107 @@ class Chain:
                 raise ValueError("workgroup size: 64, 128 or 256")
             head = ['#include "%s"' % ("w32_%s.h" % P if self.builtin else "params_%s_w32.h" % P), '#include "modarith_amd_w32.h"', '#include "capi_common.h"', '#include "kernels32.h"', "#include <utility>", "",
                     "namespace {", "using namespace ma32;", "using P = ma32::P_%s_W32;" % P]
-            shape = ["constexpr int EPT_CAP = %d;   // widest access of this build in elements per lane (4 = 16 bytes, 2 = 8, 1 = 4); wider kernels are not instantiated" % cap,
-                     "constexpr int CBLOCK = %d;   // workgroup size" % block]
-        else:
-            if block is not None:
-                raise ValueError("the workgroup size is a parameter of the 32-bit word form only")
-            heavy = (ept or self.default_ept()) == 1      # (default_ept() is 1 where an operation of _HEAVY is in the chain)
-            # one LDS image per input array of the element-major kernel while they fit 64 KB (512 (N | 1) words each), else one shared
-            # image; none above 14 limbs, where a single image does not fit (as k_convert_lds)
-            images = 0 if N > 14 else self.nin if self.nin * 512 * (N | 1) * 8 <= 65536 else 1
-            head = ['#include "params_%s.h"' % P, '#include "modarith_amd.h"', '#include "capi_common.h"', '#include "kernels.h"', "#include <utility>", "",
-                    "namespace {", "using namespace ma;", "using P = ma::P_%s;" % P]
-            shape = [] if nbytes else ["#define CHAIN_AOS_IMAGES %d   // LDS images of the element-major kernel: one per input array, 1 = one shared image, 0 = no kernel (more than 14 limbs)" % images]
-        if shared:
-            shape.append("#define CHAIN_NSHARED %d   // operands that are one element for the whole batch: host pointers after the element batches in in[], by value in the kernel arguments" % self.nshared)
+            return head, ["constexpr int EPT_CAP = %d;   // widest access of this build in elements per lane (4 = 16 bytes, 2 = 8, 1 = 4); wider kernels are not instantiated" % cap,
+                          "constexpr int CBLOCK = %d;   // workgroup size" % block], heavy
+        if block is not None:
+            raise ValueError("the workgroup size is a parameter of the 32-bit word form only")
+        heavy = (ept or self.default_ept()) == 1          # (default_ept() is 1 where an operation of _HEAVY is in the chain)
+        # one LDS image per input array of the element-major kernel while they fit 64 KB (512 (N | 1) words each), else one shared
+        # image; none above 14 limbs, where a single image does not fit (as k_convert_lds)
+        images = 0 if N > 14 else self.nin if self.nin * 512 * (N | 1) * 8 <= 65536 else 1
+        head = ['#include "params_%s.h"' % P, '#include "modarith_amd.h"', '#include "capi_common.h"', '#include "kernels.h"', "#include <utility>", "",
+                "namespace {", "using namespace ma;", "using P = ma::P_%s;" % P]
+        return head, ([] if self.bins or self.bouts else ["#define CHAIN_AOS_IMAGES %d   // LDS images of the element-major kernel: one per input array, 1 = one shared image, 0 = no kernel (more than 14 limbs)" % images]), heavy
+
+    def _defines(self, waves: int) -> List[str]:
+        """the optional #defines csrc/chain.inc reads: only those of what the chain has"""
+        L = []
+        if self.sh_idx:
+            L.append("#define CHAIN_NSHARED %d   // operands that are one element for the whole batch: host pointers after the element batches in in[], by value in the kernel arguments" % self.nshared)
         if self.pouts:
-            shape.append("#define CHAIN_NPRED %d   // int32 results, one entry per element: device arrays after the element outputs in out[]" % len(self.pouts))
+            L.append("#define CHAIN_NPRED %d   // int32 results, one entry per element: device arrays after the element outputs in out[]" % len(self.pouts))
         if self.bins:
-            shape.append("#define CHAIN_NBIN %d   // byte-record inputs: arrays of n records of P::NBYTES big-endian bytes after the element batches in in[]" % len(self.bins))
-        if nbytes:
-            shape.append("#define CHAIN_BYTES_STAGED %d   // the way to the bytes of a call on 16-byte aligned record arrays: 1 = staged through LDS, 0 = direct (fuse.BYTES_IO_DEFAULT)"
-                         % (BYTES_IO_DEFAULT[self.wl] == "staged"))
+            L.append("#define CHAIN_NBIN %d   // byte-record inputs: arrays of n records of P::NBYTES big-endian bytes after the element batches in in[]" % len(self.bins))
+        if self.bins or self.bouts:
+            L.append("#define CHAIN_BYTES_STAGED %d   // the way to the bytes of a call on 16-byte aligned record arrays: 1 = staged through LDS, 0 = direct (fuse.BYTES_IO_DEFAULT)"
+                     % (BYTES_IO_DEFAULT[self.wl] == "staged"))
         if self.bouts:
-            shape.append("#define CHAIN_NBOUT %d   // byte-record outputs: arrays of n records after the element outputs in out[]" % len(self.bouts))
+            L.append("#define CHAIN_NBOUT %d   // byte-record outputs: arrays of n records after the element outputs in out[]" % len(self.bouts))
         if waves:
-            shape.append("#define CHAIN_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(%d, %d)))" % (waves, waves))
-        args = ", ".join([("v%d" if i in shared else "v%d[E]") % i for i in range(nv)] + ["s%d[E]" % k for k in range(self.nsel + self.npred)])
+            L.append("#define CHAIN_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(%d, %d)))" % (waves, waves))
+        return L
+
+    def _body(self) -> List[str]:
+        """body<F>: the chain on one element's registers, behind the helper that some of its lines call"""
+        consts = set(self.in_idx) | set(self.sh_idx)      # what the body only reads: the element inputs and the shared operands
+        calls = self._body_lines()
+        L = [""]
+        if any("opaque(" in l for l in calls):
+            L += ["// a copy of an element that the compiler cannot see through (for a value that a second predicate reads: Chain._body_lines)",
+                  'MA_DEV void opaque(const spint* a, spint* c) { static_for<0, P::N>([&](auto I) { spint x = a[I]; asm volatile("" : "+v"(x)); c[I] = x; }); }', ""]
+        L += ["// the chain on one element's registers; F = %s" % ("Field<P> (one product policy at this word length: no vote)" if self.wl == 32 else "Field<P, FAST>"),
+              "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i in consts else "spint* v%d") % i for i in range(self.nvals)] + ["int s%d" % k for k in range(self.nsel)] + ["int& s%d" % (self.nsel + k) for k in range(self.npred)])]
+        return L + calls + ["}"]
+
+    def _vote(self, policy: str) -> List[str]:
+        """the lines of chain_step that run body<F> on each of the lane's elements: at word length 64 under the wave's vote on the inputs"""
+        shared = set(self.sh_idx)                         # one element for the whole batch: a pointer into the kernel arguments, not a per-lane array
+        args = ", ".join([("v%d" if i in shared else "v%d[E]") % i for i in range(self.nvals)] + ["s%d[E]" % k for k in range(self.nsel + self.npred)])
+        if self.wl == 32:
+            return ["    static_for<0, EPT>([&](auto E) { body<Field<P>>(%s); });" % args]
         # modint of a negative int is the word (spint)k, outside the limb contract at 64 bits: such a chain runs the exact products, as Field.modint does
-        if policy == "vote" and any(o[0] == "modint" and o[4] < 0 for o in self.ops):
+        if policy == "vote" and any(o.op == "modint" and o.imm < 0 for o in self.ops):
             policy = "exact"
-        if w32:
-            run = ["    static_for<0, EPT>([&](auto E) { body<Field<P>>(%s); });" % args]
-        else:
-            run = ["    bool fast = %s;" % ("true" if policy == "fast" else "false"),
-                   "    if constexpr (P::SPLIT > 0 && %s) {" % ("true" if policy == "vote" else "false"),
-                   "        bool ok = %s;" % (" && ".join("in_split_contract<P>(v%d)" % i for i in self.sh_idx) or "true"),
-                   "        static_for<0, EPT>([&](auto E) { ok = ok && " + " && ".join("in_split_contract<P>(v%d[E])" % i for i in self.in_idx + [b[0] for b in self.bins]) + "; });",
-                   "        fast = __all(ok);",
-                   "    }",
-                   "    if (fast) {",
-                   "        static_for<0, EPT>([&](auto E) { body<Field<P, true>>(%s); });" % args,
-                   "    } else {",
-                   "        static_for<0, EPT>([&](auto E) { body<Field<P, false>>(%s); });" % args,
-                   "    }"]
-        L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s%s: %d inputs%s, %d operations, %d outputs%s; kernels and entry bodies: csrc/chain.inc"
-             % (self.name, P, ", 32-bit word form" if w32 else "", self.nin, ", %d shared" % self.nshared if shared else "", len(self.ops), len(self.outs), (", %d int outputs" % len(self.pouts) if self.pouts else "") + (", %d byte inputs, %d byte outputs" % (len(self.bins), len(self.bouts)) if nbytes else ""))]
-        L += head + ['#define CHAIN_SYMBOL "%s"   // the entry points: <this>_batch%s' % (self.symbol[:-6], "" if w32 else ", <this>_aos"),
-                     "constexpr int NIN = %d, NOUT = %d, NSEL = %d;" % (self.nin, len(self.outs), self.nsel),
-                     "constexpr bool HEAVY = %s;   // one element per lane on every batch: an inversion, a progenitor or a square root in the chain%s"
-                     % ("true" if heavy else "false", "" if w32 else ", or build(ept=1)")] + shape
-        L += ["", "// the chain on one element's registers; F = %s" % ("Field<P> (one product policy at this word length: no vote)" if w32 else "Field<P, FAST>"),
-              "template <class F> MA_DEV void body(%s) {" % ", ".join([("const spint* v%d" if i in consts else "spint* v%d") % i for i in range(nv)] + ["int s%d" % k for k in range(self.nsel)] + ["int& s%d" % (self.nsel + k) for k in range(self.npred)])]
-        body = self._body_lines()
-        if any("opaque(" in l for l in body):
-            L[-2:-2] = ["// a copy of an element that the compiler cannot see through (for a value that a second predicate reads: Chain._body_lines)",
-                        'MA_DEV void opaque(const spint* a, spint* c) { static_for<0, P::N>([&](auto I) { spint x = a[I]; asm volatile("" : "+v"(x)); c[I] = x; }); }', ""]
-        L += body
-        L += ["}", "", "// EPT elements of a lane through the chain; io is how the calling kernel of csrc/chain.inc reaches them in memory",
-              "template <int EPT, class IO> MA_DEV void chain_step(IO io) {",
-              "    " + " ".join("spint v%d[EPT][P::N];" % i for i in range(nv) if i not in shared)]
+        return ["    bool fast = %s;" % ("true" if policy == "fast" else "false"),
+                "    if constexpr (P::SPLIT > 0 && %s) {" % ("true" if policy == "vote" else "false"),
+                "        bool ok = %s;" % (" && ".join("in_split_contract<P>(v%d)" % i for i in self.sh_idx) or "true"),
+                "        static_for<0, EPT>([&](auto E) { ok = ok && " + " && ".join("in_split_contract<P>(v%d[E])" % i for i in self.in_idx + [b[0] for b in self.bins]) + "; });",
+                "        fast = __all(ok);",
+                "    }",
+                "    if (fast) {",
+                "        static_for<0, EPT>([&](auto E) { body<Field<P, true>>(%s); });" % args,
+                "    } else {",
+                "        static_for<0, EPT>([&](auto E) { body<Field<P, false>>(%s); });" % args,
+                "    }"]
+
+    def _step(self, policy: str) -> List[str]:
+        """chain_step<EPT, IO>: the lane's elements in through io, the chain, the results out through io"""
+        L = ["", "// EPT elements of a lane through the chain; io is how the calling kernel of csrc/chain.inc reaches them in memory",
+             "template <int EPT, class IO> MA_DEV void chain_step(IO io) {",
+             "    " + " ".join("spint v%d[EPT][P::N];" % i for i in range(self.nvals) if i not in self.sh_idx)]
         L += ["    io.load(%d, v%d);" % (k, i) for k, i in enumerate(self.in_idx)]
         L += ["    const spint* v%d = io.shared(%d);" % (i, k) for k, i in enumerate(self.sh_idx)]
         L += ["    int s%d[EPT]; io.sel(%d, s%d);" % (k, k, k) for k in range(self.nsel)]
         L += ["    int s%d[EPT];" % (self.nsel + k) for k in range(self.npred)]
         L += ["    io.imp(%d, v%d, s%d);" % (k, i, self.nsel + f) for k, (i, f) in enumerate(self.bins)]
-        L += run
+        L += self._vote(policy)
         L += ["    io.store(%d, v%d);" % (k, o) for k, o in enumerate(self.outs)]
         L += ["    io.exp(%d, v%d);" % (k, t) for k, (_, t) in enumerate(self.bouts)]
         L += ["    io.pred(%d, s%d);" % (k, o) for k, o in enumerate(self.pouts)]
-        L += ["}", '#include "chain.inc"', "}  // namespace", "",
-              'extern "C" int %s(const void* const* in, void* const* out, size_t n, size_t ld, void* stream) { return %s(in, out, n, ld, stream); }' % (self.symbol, "chain_bytes_batch" if nbytes else "chain_batch")]
+        return L + ["}"]
+
+    def source(self, ept: Optional[int] = None, policy: str = "vote", waves: int = 0, block: Optional[int] = None) -> str:
+        """The unit: what depends on the chain -- constants, body<F> and chain_step<EPT, IO> -- around csrc/chain.inc, which holds the
+        kernels (k_chain<EPT>, k_chain_aos) and the bodies of the entry points for both word lengths.
+        ept: elements per lane on aligned batches (2 = 16-byte accesses, 1 = 8-byte; at word length 32: 4 / 2 / 1 = 16 / 8 / 4 bytes);
+        None = the measured default.  block: workgroup size, word length 32 only"""
+        if not (self.nin or self.bins) or not (self.outs or self.pouts or self.bouts):
+            raise ValueError("a chain needs at least one input and one output")
+        w32, nbytes = self.wl == 32, len(self.bins) + len(self.bouts)
+        head, shape, heavy = self._shape(ept, policy, block)
+        entry = "const void* const* in, void* const* out, size_t n, "
+        L = ["// GENERATED by modarith_amd/fuse.py -- do not edit.  Chain %r over %s%s: %d inputs%s, %d operations, %d outputs%s; kernels and entry bodies: csrc/chain.inc"
+             % (self.name, self.prime, ", 32-bit word form" if w32 else "", self.nin, ", %d shared" % self.nshared if self.sh_idx else "", len(self.ops), len(self.outs),
+                (", %d int outputs" % len(self.pouts) if self.pouts else "") + (", %d byte inputs, %d byte outputs" % (len(self.bins), len(self.bouts)) if nbytes else ""))]
+        L += head + ['#define CHAIN_SYMBOL "%s"   // the entry points: <this>_batch%s' % (self.symbol[:-6], "" if w32 else ", <this>_aos"),
+                     "constexpr int NIN = %d, NOUT = %d, NSEL = %d;" % (self.nin, len(self.outs), self.nsel),
+                     "constexpr bool HEAVY = %s;   // one element per lane on every batch: an inversion, a progenitor or a square root in the chain%s"
+                     % ("true" if heavy else "false", "" if w32 else ", or build(ept=1)")]
+        L += shape + self._defines(waves) + self._body() + self._step(policy)
+        L += ['#include "chain.inc"', "}  // namespace", "",
+              'extern "C" int %s(%ssize_t ld, void* stream) { return chain_batch(in, out, n, ld, stream); }' % (self.symbol, entry)]
         if not w32:
-            L += ['extern "C" int %s(const void* const* in, void* const* out, size_t n, void* stream) { return chain_aos(in, out, n, stream); }' % self.aos_symbol]
+            L += ['extern "C" int %s(%svoid* stream) { return chain_aos(in, out, n, stream); }' % (self.aos_symbol, entry)]
         return "\n".join(L + [""])
 
     @property
@@ -525,6 +554,16 @@ class Chain:
         if self.wl == 32:
             raise ValueError("the element-major entry is not built at word length 32: convert with modarith_amd_w32_aos_to_soa and call %s" % self.symbol)
         return "chain_%s_%s_aos" % (self.name, self.prime)
+
+    def prototype(self) -> str:
+        """the C declaration of the _batch entry, with what layout() says `in` and `out` hold"""
+        ins, outs = self.layout()
+        recs = ", then %%d arrays of n records of %d bytes" % self.params.nbytes
+        say = lambda kinds, texts: "".join(t % kinds[kind] for kind, t in texts if kinds[kind])
+        rest = say(outs, (("bytes", recs), ("ints", ", then %d int32 arrays of n entries")))
+        return ("int %s(const void *const *in /* %d element batches%s */, void *const *out /* %d%s */, size_t n, size_t ld, void *stream);"
+                % (self.symbol, ins["elements"], say(ins, (("bytes", recs), ("shared", ", then %%d host pointers to shared operands of %d limbs" % self.params.nlimbs),
+                                                           ("selectors", ", then %d int32 selector arrays"))), outs["elements"], " element batches" + rest if rest else ""))
 
     # ------------------------------------------------------------------ building the plug-in
     def lib_path(self, plugin_dir: Optional[str] = None) -> str:
@@ -540,10 +579,11 @@ class Chain:
         src, obj, meta = (os.path.join(d, base + e) for e in (".hip", ".o", ".json"))
         lib = self.lib_path(d)
         emit._write(src, src_text)
-        record = {"chain": self.name, "prime": self.prime, "wl": self.wl, "inputs": self.nin, "shared": self.nshared, "selectors": self.nsel,
-                  "outputs": len(self.outs), "preds": len(self.pouts), "ops": [o[0] for o in self.ops], "symbol": self.symbol}
-        if self.bins or self.bouts:
-            record.update(bytes_in=len(self.bins), bytes_out=len(self.bouts))
+        ins, outs = self.layout()
+        record = {"chain": self.name, "prime": self.prime, "wl": self.wl, "inputs": ins["elements"], "shared": ins["shared"], "selectors": ins["selectors"],
+                  "outputs": outs["elements"], "preds": outs["ints"], "ops": [o.op for o in self.ops], "symbol": self.symbol}
+        if ins["bytes"] or outs["bytes"]:
+            record.update(bytes_in=ins["bytes"], bytes_out=outs["bytes"])
         # A chain that computes ints is compiled without the SLP vectoriser: at two elements per lane it pairs the limbs of the two elements'
         # redc (they arrive as the halves of one 16-byte load) into vector operations and the kernel of four predicates over P-256 comes to
         # 380 registers instead of 119.  Chains without ints are compiled as they always were
@@ -553,10 +593,10 @@ class Chain:
 
 
 class FusedChain:
-    """a built chain: call it with one device batch per input (flat [N, n] or tiled [n / tile, N, tile], all the same shape; int64
-    limbs, or int32 for a chain of the 32-bit word form), then one host element per shared operand (Nlimbs ints or a CPU integer
-    tensor, as Field.modmuls takes b0), then one int32 device array per selector.  Returns the element outputs, then one int32 [n]
-    tensor per int output (ch.output() of a Pred); `out=` takes them in that order"""
+    """a built chain: call it with the arrays of Chain.layout(), in its order -- element batches are flat [N, n] or tiled [n / tile, N,
+    tile], all the same shape (int64 limbs, or int32 for a chain of the 32-bit word form), byte records uint8 [n, Nbytes], a shared
+    operand Nlimbs ints or a CPU integer tensor (as Field.modmuls takes b0), selectors int32 [n] on the device.  Returns the output
+    arrays in the layout's order; `out=` takes them in that order"""
     def __init__(self, chain: Chain, lib: str, built: bool):
         self.chain, self.path, self.built = chain, lib, built
         _lib.load()
@@ -566,15 +606,24 @@ class FusedChain:
         self.fn.restype = ctypes.c_int
         self._fields = {}
 
+    @staticmethod
+    def _cut(arrays, kinds):
+        """the arrays of one side of a call, one list per kind of that side of Chain.layout(); None where the count is not the layout's"""
+        if len(arrays) != sum(kinds.values()):
+            return None
+        it = iter(arrays)
+        return [[next(it) for _ in range(count)] for count in kinds.values()]
+
     def _split(self, inputs, what: str):
         ch = self.chain
-        nb = len(ch.bins)
-        if len(inputs) != ch.nin + nb + ch.nshared + ch.nsel:
+        kinds = ch.layout()[0]
+        cut = self._cut(inputs, kinds)
+        if cut is None:
             raise ValueError("chain %s takes %d element %s%s followed by %d shared operands (%d limbs each, on the host) and %d int32 selector arrays"
-                             % (ch.name, ch.nin, what, ", %d arrays of byte records (uint8 [n, %d])" % (nb, ch.params.nbytes) if nb else "",
-                                ch.nshared, ch.params.nlimbs, ch.nsel))
-        k = ch.nin + nb
-        return inputs[:ch.nin], list(inputs[ch.nin:k]), [self._limbs(b) for b in inputs[k:k + ch.nshared]], inputs[k + ch.nshared:]
+                             % (ch.name, kinds["elements"], what, ", %d arrays of byte records (uint8 [n, %d])" % (kinds["bytes"], ch.params.nbytes) if kinds["bytes"] else "",
+                                kinds["shared"], ch.params.nlimbs, kinds["selectors"]))
+        elems, recs, shared, sels = cut
+        return elems, recs, [self._limbs(b) for b in shared], sels
 
     def _limbs(self, b):
         """one shared operand as host words of the chain's word length: a sequence of Nlimbs ints or a CPU integer tensor, as Field.modmuls takes b0"""
@@ -590,43 +639,46 @@ class FusedChain:
         return (word * len(b))(*[v & ((1 << ch.wl) - 1) for v in b])          # (signed tensors hold the same words)
 
     def _outs(self, out, n: int, like, fresh):
-        """the arrays of out[]: the element outputs (fresh() each where the caller gives none), then one uint8 [n, Nbytes] per byte output,
-        then one int32 [n] per int output"""
+        """the output arrays of a call, one list per kind of Chain.layout(): the caller's, or new ones -- fresh() per element output, uint8
+        [n, Nbytes] per byte output, int32 [n] per int output"""
         import torch
         ch = self.chain
-        outs = list(out) if out is not None else ([fresh() for _ in ch.outs] + [torch.empty((n, ch.params.nbytes), dtype=torch.uint8, device=like.device) for _ in ch.bouts]
-                                                  + [torch.empty(n, dtype=torch.int32, device=like.device) for _ in ch.pouts])
-        if len(outs) != len(ch.outs) + len(ch.bouts) + len(ch.pouts):
-            raise ValueError("chain %s has %d outputs%s%s" % (ch.name, len(ch.outs), " followed by %d byte-record outputs" % len(ch.bouts) if ch.bouts else "",
-                                                              " followed by %d int32 outputs" % len(ch.pouts) if ch.pouts else ""))
-        return outs
+        kinds = ch.layout()[1]
+        make = {"elements": fresh, "bytes": lambda: torch.empty((n, ch.params.nbytes), dtype=torch.uint8, device=like.device),
+                "ints": lambda: torch.empty(n, dtype=torch.int32, device=like.device)}
+        cut = self._cut(list(out) if out is not None else [make[kind]() for kind, count in kinds.items() for _ in range(count)], kinds)
+        if cut is None:
+            raise ValueError("chain %s has %d outputs%s%s" % (ch.name, kinds["elements"], " followed by %d byte-record outputs" % kinds["bytes"] if kinds["bytes"] else "",
+                                                              " followed by %d int32 outputs" % kinds["ints"] if kinds["ints"] else ""))
+        return cut
 
-    def _run(self, fn, symbol: str, elems, shared, sels, outs, n: int, *ld, device=None, recs=()):
-        """what both entries share: the selector check, the pointer arrays and the call on the current stream of the batches' device.
+    def _run(self, fn, symbol: str, ins, outs, n: int, *ld, device=None):
+        """what both entries share: the checks of the arrays that are not element batches, the pointer arrays and the call on the current
+        stream of the batches' device.  ins, outs: one list per kind, as _split and _outs give them.
         The entry point reads the shared operands' limbs before it returns: the host arrays need to live no longer than this call"""
         import torch
+        elems, recs, _, sels = ins
         for d in sels:
             if d.dtype != torch.int32 or d.numel() != n or not d.is_cuda or not d.is_contiguous() or (device is not None and d.device != device):
                 raise ValueError("selectors are contiguous int32 device tensors with one 0/1 entry per element")
         ch = self.chain
         dev = device if device is not None else (elems[0] if elems else recs[0]).device
-        k = len(ch.outs) + len(ch.bouts)
-        for r in list(recs) + outs[len(ch.outs):k]:
+        for r in recs + outs[1]:
             if r.dtype != torch.uint8 or r.dim() != 2 or tuple(r.shape) != (n, ch.params.nbytes) or not r.is_cuda or not r.is_contiguous() or r.device != dev:
                 raise ValueError("byte records are contiguous uint8 tensors [n, %d] on the batches' device" % ch.params.nbytes)
-        for d in outs[k:]:
+        for d in outs[2]:
             if d.dtype != torch.int32 or d.dim() != 1 or d.numel() != n or not d.is_cuda or not d.is_contiguous() or d.device != dev:
                 raise ValueError("int outputs are contiguous int32 tensors of n entries on the batches' device")
-        ptrs = [t.data_ptr() for t in elems] + [t.data_ptr() for t in recs] + [ctypes.addressof(b) for b in shared] + [t.data_ptr() for t in sels]
-        ins = (ctypes.c_void_p * len(ptrs))(*ptrs)
-        ous = (ctypes.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
+        flat = [t for kind in outs for t in kind]
+        ptrs = [ctypes.addressof(t) if kind == "shared" else t.data_ptr() for kind, arrays in zip(ch.layout()[0], ins) for t in arrays]
         with torch.cuda.device(dev):
-            _lib.check(fn(ins, ous, n, *ld, torch.cuda.current_stream(dev).cuda_stream), symbol)
-        return tuple(outs)
+            _lib.check(fn((ctypes.c_void_p * len(ptrs))(*ptrs), (ctypes.c_void_p * len(flat))(*[t.data_ptr() for t in flat]), n, *ld,
+                          torch.cuda.current_stream(dev).cuda_stream), symbol)
+        return tuple(flat)
 
     def aos(self, *inputs, out: Optional[Sequence] = None):
         """the same chain over element-major device arrays int64 [n, Nlimbs] (`spint x[n][Nlimbs]`, how CPU callers of field.c hold
-        elements): no aos_to_soa / soa_to_aos passes around it; shared operands and selectors follow the element arrays as in __call__"""
+        elements): no aos_to_soa / soa_to_aos passes around it; the other arrays as in __call__"""
         import torch
         ch = self.chain
         N = ch.params.nlimbs
@@ -634,21 +686,23 @@ class FusedChain:
             raise ValueError("a chain with byte records has no element-major entry; call %s" % ch.symbol)
         if ch.wl == 32:
             raise ValueError("the element-major entry is not built at word length 32: convert with modarith_amd_w32_aos_to_soa and call %s" % ch.symbol)
-        elems, _, shared, sels = self._split(inputs, "arrays")
+        ins = self._split(inputs, "arrays")
+        elems = ins[0]
         n = elems[0].shape[0]
         outs = self._outs(out, n, elems[0], lambda: torch.empty_like(elems[0]))
-        for t in list(elems) + outs[:len(ch.outs)]:
+        for t in elems + outs[0]:
             if t.dtype != torch.int64 or t.dim() != 2 or tuple(t.shape) != (n, N) or not t.is_cuda or not t.is_contiguous():
                 raise ValueError("expected contiguous int64 device tensors of shape [n, %d]" % N)
         fn = getattr(self.lib, ch.aos_symbol)
         fn.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_void_p]
         fn.restype = ctypes.c_int
-        return self._run(fn, ch.aos_symbol, elems, shared, sels, outs, n)
+        return self._run(fn, ch.aos_symbol, ins, outs, n)
 
     def __call__(self, *inputs, out: Optional[Sequence] = None, device=None):
         from .field import Field
         ch = self.chain
-        inputs, recs, shared, sels = self._split(inputs, "batches")
+        ins = self._split(inputs, "batches")
+        inputs, recs = ins[:2]
         dev = device if device is not None else (inputs[0] if inputs else recs[0]).device
         F = self._fields.get(dev)
         if F is None:                                  # binding a Field derives the prime's constants: once per device, not per call
@@ -659,10 +713,10 @@ class FusedChain:
         else:
             n = F._chk(*inputs) if inputs else recs[0].shape[0]
             outs = self._outs(out, n, inputs[0] if inputs else recs[0], lambda: F._out(inputs[0], None))
-        elems = list(inputs) + outs[:len(ch.outs)]
+        elems = inputs + outs[0]
         if elems and F._chk(*elems) != n:
             raise ValueError("the element batches hold %d elements, the byte records %d" % (F._chk(*elems), n))
-        return self._run(self.fn, ch.symbol, inputs, shared, sels, outs, n, F._ld(elems[0]) if elems else n, device=F.device, recs=recs)
+        return self._run(self.fn, ch.symbol, ins, outs, n, F._ld(elems[0]) if elems else n, device=F.device)
 
 
 def bench_chain(prime: str = "X25519") -> Chain:
@@ -789,26 +843,18 @@ def parse(prime: str, name: str, text: str, wl: int = 64) -> Chain:
             return getattr(ch, fn)(*[ev(a) for a in node.args])
         raise ValueError("cannot parse %r" % ast.unparse(node))
 
+    declare = {"in": ch.input, "shared": ch.shared, "sel": ch.selector, "bytes": ch.input_bytes}
+    emit_as = {"out": ch.output, "outbytes": ch.output_bytes}
     for st in [t.strip() for t in text.split(";") if t.strip()]:
         head, _, rest = st.partition(" ")
-        if head == "in":
+        if head in declare:
             for nm in [t.strip() for t in rest.split(",")]:
-                env[nm] = ch.input()
-        elif head == "shared":
-            for nm in [t.strip() for t in rest.split(",")]:
-                env[nm] = ch.shared()
-        elif head == "sel":
-            for nm in [t.strip() for t in rest.split(",")]:
-                env[nm] = ch.selector()
-        elif head == "bytes":
-            for nm in [t.strip() for t in rest.split(",")]:
-                env[nm], flags[nm] = ch.input_bytes()
-        elif head == "out":
+                env[nm] = declare[head]()
+                if head == "bytes":                             # (the value and modimp's return value)
+                    env[nm], flags[nm] = env[nm]
+        elif head in emit_as:
             for node in ast.parse("(%s,)" % rest, mode="eval").body.elts:
-                ch.output(ev(node))
-        elif head == "outbytes":
-            for node in ast.parse("(%s,)" % rest, mode="eval").body.elts:
-                ch.output_bytes(ev(node))
+                emit_as[head](ev(node))
         else:
             node = ast.parse(st).body[0]
             if not isinstance(node, ast.Assign) or len(node.targets) != 1:
@@ -843,11 +889,7 @@ def main(argv: List[str]) -> int:
         print(e)
         return 2
     print("%s %s" % ("built" if f.built else "up to date:", f.path))
-    recs = lambda k: (", then %d arrays of n records of %d bytes" % (k, ch.params.nbytes)) if k else ""
-    print("int %s(const void *const *in /* %d element batches%s%s%s */, void *const *out /* %d%s */, size_t n, size_t ld, void *stream);"
-          % (ch.symbol, ch.nin, recs(len(ch.bins)), (", then %d host pointers to shared operands of %d limbs" % (ch.nshared, ch.params.nlimbs)) if ch.nshared else "",
-             (", then %d int32 selector arrays" % ch.nsel) if ch.nsel else "", len(ch.outs),
-             ((" element batches" + recs(len(ch.bouts)) + (", then %d int32 arrays of n entries" % len(ch.pouts) if ch.pouts else "")) if ch.pouts or ch.bouts else "")))
+    print(ch.prototype())
     if ch.wl == 64 and not (ch.bins or ch.bouts):
         print("int %s(const void *const *in, void *const *out, size_t n, void *stream);   /* the same over element-major arrays x[n][Nlimbs] */" % ch.aos_symbol)
     print("HBM bytes per element: %d fused, %d call by call" % (ch.traffic_bytes(), ch.unfused_traffic_bytes()))

@@ -79,6 +79,79 @@ def test_unit_holds_the_chain_and_includes_the_frame_once(wl):
     inc = open(os.path.join(build.CSRC, "chain.inc")).read()
     assert inc.count("void k_chain(Args A, size_t nthreads, Ld L)") == 1 and inc.count("void k_chain_aos(Args A, size_t n)") == 1
     assert inc.count("int chain_batch(") == 1 and inc.count("void aos_in(") == 1
+    # one entry body for chains with and without byte records, and one check of the tiled stride in it
+    assert "chain_bytes_batch" not in inc and inc.count("must be a power of two >= 128") == 1
+    by = Chain("X25519", "by", wl=wl)
+    v, _ = by.input_bytes()
+    by.output_bytes(by.modsqr(v))
+    bsrc = by.source()
+    assert "chain_bytes_batch" not in bsrc and bsrc.count("{ return chain_batch(in, out, n, ld, stream); }") == 1
+
+
+class _Arr:
+    """stands for an array where only the count of a call's arrays is looked at"""
+
+
+def test_layout_is_the_one_order_of_a_calls_arrays(tmp_path):
+    """Chain.layout() against what FusedChain demands and makes and what prototype() (the line `python -m modarith_amd.fuse` prints)
+    says, on a chain with every kind of array -- two of every kind but the element input, so that no two counts are equal by chance --;
+    every wrong count is refused with the message it always had"""
+    import re
+    from modarith_amd.fuse import FusedChain
+    ch = Chain("X25519", "kinds")
+    a, b, c = ch.inputs(3)
+    (r, ok), (q, _) = ch.input_bytes(), ch.input_bytes()
+    k, k2 = ch.shared(), ch.shared()
+    d, d2 = ch.selector(), ch.selector()
+    t = ch.modmul(ch.modadd(a, b), ch.modmul(k, k2))
+    u = ch.modadd(ch.modadd(t, r), ch.modadd(q, c))
+    for v in (ch.modcmv(d, t, u), ch.modcmv(d2, u, t)):
+        ch.output(v)
+    for v in (u, t):
+        ch.output_bytes(v)
+    for p in (ch.land(ok, ch.lnot(ch.modis0(u))), ch.modis0(t)):
+        ch.output(p)
+    ins, outs = ch.layout()
+    assert list(ins.items()) == [("elements", 3), ("bytes", 2), ("shared", 2), ("selectors", 2)]
+    assert list(outs.items()) == [("elements", 2), ("bytes", 2), ("ints", 2)]
+    assert (ch.nin, len(ch.bins), ch.nshared, ch.nsel, len(ch.outs), len(ch.bouts), len(ch.pouts)) == (3, 2, 2, 2, 2, 2, 2)
+    # the printed prototype: the numbers inside the two comments, in order
+    proto = ch.prototype()
+    cin, cout = re.findall(r"/\* (.*?) \*/", proto)
+    assert proto.startswith("int chain_kinds_X25519_batch(const void *const *in /* 3 element batches, then 2 arrays of n records of 32 bytes, then 2 host pointers")
+    assert [int(x) for x in re.findall(r"\d+", cin)] == [3, 2, 32, 2, 5, 2, 32] and "then 2 int32 selector arrays" in cin          # (32 bytes, 5 limbs, int32)
+    assert cout == "2 element batches, then 2 arrays of n records of 32 bytes, then 2 int32 arrays of n entries"
+    plain = Chain("X25519", "plain")
+    x, y = plain.inputs(2)
+    plain.output(plain.modmul(x, y))
+    assert "/* 2 element batches */, void *const *out /* 1 */" in plain.prototype()
+    # what a built chain demands of a call and makes for it (nothing is built or loaded here)
+    f = FusedChain.__new__(FusedChain)
+    f.chain = ch
+    limbs = [1, 2, 3, 4, 5]
+    good = [_Arr() for _ in range(5)] + [limbs, limbs] + [_Arr(), _Arr()]
+    elems, recs, shared, sels = f._split(good, "batches")
+    assert (elems, recs, sels) == (good[:3], good[3:5], good[7:]) and [list(s) for s in shared] == [limbs, limbs]
+    assert sum(ins.values()) == len(good) == 9
+    for bad in (good[:-1], good + [_Arr()], []):
+        with pytest.raises(ValueError, match=r"chain kinds takes 3 element batches, 2 arrays of byte records \(uint8 \[n, 32\]\) followed by 2 shared operands "
+                                             r"\(5 limbs each, on the host\) and 2 int32 selector arrays"):
+            f._split(bad, "batches")
+    import torch
+    like = torch.empty(0)
+    eouts, brecs, ints = f._outs(None, 7, like, lambda: "element batch")
+    made = eouts + brecs + ints
+    assert len(made) == sum(outs.values()) == 6 and eouts == ["element batch"] * 2
+    assert [(t.dtype, tuple(t.shape)) for t in brecs + ints] == [(torch.uint8, (7, 32))] * 2 + [(torch.int32, (7,))] * 2
+    assert f._outs(made, 7, like, None) == [eouts, brecs, ints]
+    for bad in (made[:-1], made + [made[-1]], []):
+        with pytest.raises(ValueError, match="chain kinds has 2 outputs followed by 2 byte-record outputs followed by 2 int32 outputs"):
+            f._outs(bad, 7, like, None)
+    f.chain = plain
+    with pytest.raises(ValueError, match=r"chain plain takes 2 element arrays followed by 0 shared operands \(5 limbs each, on the host\) and 0 int32 selector arrays"):
+        f._split([_Arr()], "arrays")
+    with pytest.raises(ValueError, match="chain plain has 1 outputs$"):
+        f._outs([], 7, like, None)
 
 
 @pytest.mark.parametrize("wl", [64, 32])

@@ -279,6 +279,78 @@ def test_neighbours_outside_the_limb_contract(ctx, torch_cuda, monkeypatch, path
         assert torch.equal(got, want), width
 
 
+# ---------------------------------------------------------------------------------------------------------------- every kind of array in one call
+EVERY = "in a; bytes r; shared k; sel d; t = modmul(a, k); u = modadd(t, r); out modcmv(d, t, u); outbytes u; out flag(r) & (not modis0(u))"
+EVERY_N = 640                                                    # the pool: every batch below is a prefix of it
+SENTINEL = 0x5a
+
+
+def _misaligned(torch, t, wl):
+    """the flat batch t, rows and all, one word behind a 16-byte aligned address (_at on its bytes)"""
+    return _at(torch, t.view(torch.uint8), wl // 8).view(t.dtype)
+
+
+@pytest.mark.parametrize("P,wl,width", [("X25519", 64, None), ("NIST256", 32, None), ("NIST256", 32, 2)], ids=("X25519-w64", "NIST256-w32", "NIST256-w32-ept2"))
+def test_every_kind_of_array(torch_cuda, monkeypatch, P, wl, width):
+    """an element batch, a byte record, a shared operand and a selector in; an element batch, a byte record and an int out: every slot of
+    in[] and out[] at once, through the main launch and the remainder launch of the one entry body.  The element batches are views of
+    rows of EVERY_N words (an even stride: two elements per lane where the width allows, so that n = 1, 3, 513 are the remainder alone,
+    the remainder after one lane, and after more than one workgroup of lanes); every output is a view of a buffer one element longer,
+    whose last element must stay what it was"""
+    from modarith_amd import generate as gen
+    from modarith_amd.field import Field
+    from modarith_amd.fuse import parse
+    from tests.test_gpu_fuse_shared import _bcast, _elements
+    torch = torch_cuda
+    ch = parse(P, "every_by", EVERY, wl=wl)
+    f = ch.build() if width is None else ch.build(plugin_dir=os.path.join(gen.PLUGIN_DIR, "bytes_ept%d" % width), ept=width)
+    F = Field(P, wl=wl, tile=None)
+    N, nb, n0 = F.N, F.nbytes, EVERY_N
+    # the inputs, and the truth call by call through Field, once
+    a = _batch(torch, P, wl, n0, 21)
+    R = _records(torch, _pool(P, wl, 22)[:n0], nb)
+    for j in (1, 300, n0 - 1):                                   # u = 0 there: both values of modis0
+        a[:, j] = 0
+        R[j] = 0
+    k = _elements(P, wl, 1, 23)[0]
+    d = torch.randint(0, 2, (n0,), dtype=torch.int32, device="cuda", generator=torch.Generator(device="cuda").manual_seed(24))
+    r, ok = F.modimp(R)
+    t = F.modmul(a, _bcast(torch, wl, k, a))
+    u = F.modadd(t, r)
+    want_e = u.clone()
+    F.modcmv(d, t, want_e)
+    want_b, want_i = F.modexp(u), ok & (1 - F.modis0(u))
+    assert 0 < int(want_i.sum()) < n0 and 0 < int(ok.sum()) < n0 and 0 < int(d.sum()) < n0 and int(F.modis0(u).sum()) == 3
+
+    def run(n, ain, ebuf, eout, what):
+        bbuf = torch.full((n + 1, nb), SENTINEL, dtype=torch.uint8, device="cuda")
+        ibuf = torch.full((n + 1,), SENTINEL, dtype=torch.int32, device="cuda")
+        got = f(ain, R[:n], k, d[:n], out=[eout, bbuf[:n], ibuf[:n]])
+        assert got[0] is eout
+        assert torch.equal(F.to_flat(eout), want_e[:, :n]) and torch.equal(bbuf[:n], want_b[:n]) and torch.equal(ibuf[:n], want_i[:n]), what
+        assert bool((bbuf[n] == SENTINEL).all()) and int(ibuf[n]) == SENTINEL, what
+        return ebuf
+
+    for path in PATHS:
+        monkeypatch.setenv("MA_CHAIN_BYTES", path)
+        for n in (1, 3, 513):
+            ebuf = torch.full((N, n0), SENTINEL, dtype=a.dtype, device="cuda")
+            run(n, a[:, :n], ebuf, ebuf[:, :n], (path, n))
+            assert bool((ebuf[:, n:] == SENTINEL).all()), (path, n)
+        # tiled, at the smallest tile: the output's tiles are the first of a buffer of one tile more
+        tile = 128
+        ebuf = torch.full((n0 // tile + 1, N, tile), SENTINEL, dtype=a.dtype, device="cuda")
+        run(n0, F.to_tiled(a, tile), ebuf, ebuf[:n0 // tile], (path, "tiled"))
+        assert bool((ebuf[n0 // tile] == SENTINEL).all()), (path, "tiled")
+        # element arrays one word off 16-byte alignment: one element per lane whatever the build's width
+        n = 513
+        ain = _misaligned(torch, a, wl)
+        ebuf = _misaligned(torch, torch.full((N, n0), SENTINEL, dtype=a.dtype, device="cuda"), wl)
+        assert ain.data_ptr() % 16 == wl // 8 == ebuf.data_ptr() % 16
+        run(n, ain[:, :n], ebuf, ebuf[:, :n], (path, "misaligned"))
+        assert bool((ebuf[:, n:] == SENTINEL).all()), (path, "misaligned")
+
+
 # ---------------------------------------------------------------------------------------------------------------- the chain the library carries
 def _multiples(c, count):
     """G, 2G, ... in affine coordinates with Python integers (a = -3)"""

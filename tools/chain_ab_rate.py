@@ -11,7 +11,7 @@ Timed: bench_prod / X25519 through _batch (2^24 elements on tiles of 4096) and _
 shape (2^24 on tiles of 4096); device events around single launches, parent / parent copy / new alternating, warm-up first, 25 launches
 each, medians; every kernel's output is compared with the call-by-call sequence before it is timed.  Bound: new <= parent * (1 + m),
 m = twice the relative difference of the two parent copies' medians in the same run (docs/measurement.md: placement moves these kernels by
-more than code does).  Exit status 1 where a case misses it.  profiles/chain_one_include.json "rate" is this tool's output."""
+more than code does).  Exit status 1 where a case misses it.  "rate" of profiles/chain_one_include.json and of profiles/chain_one_entry.json is this tool's output."""
 import argparse
 import json
 import os
