@@ -11,6 +11,9 @@
 //   #define CHAIN_NPRED k                                                 optional: int32 results (ch.output() of a Pred), one entry per element
 //   #define CHAIN_NBIN k, CHAIN_NBOUT k                                   optional: byte-record inputs (ch.input_bytes()) and outputs (ch.output_bytes())
 //   #define CHAIN_BYTES_STAGED 0 | 1                                      with either of them: the default way to the bytes (section "byte records")
+//   #define CHAIN_BIN_LE m, CHAIN_BOUT_LE m                               optional: bit j set = byte array j of that side is little-endian
+//   #define CHAIN_BIN_SIGN m, CHAIN_BOUT_SIGN m                           optional: bit j set = the top bit of array j's records is a sign:
+//                                                                         io.imp(j, v, s, sign) takes it out, io.exp(k, v, sign) puts it in
 //   template <class F> MA_DEV void body(v0, ..., s0, ...);                the chain on one element's registers
 //   template <int EPT, class IO> MA_DEV void chain_step(IO io);           EPT elements of a lane: io.load(i, v_i) per input, io.shared(j)
 //                                                                         per shared operand, io.sel(k, s_k) per selector, the vote,
@@ -60,8 +63,9 @@ static_assert(CHAIN_NSHARED >= 0 && CHAIN_NSHARED <= 8, "a chain takes at most 8
 #define CHAIN_NPRED 0
 #endif
 // Byte records (CHAIN_NBIN + CHAIN_NBOUT > 0): arrays of n big-endian records of P::NBYTES bytes, rec[j * NBYTES + i], what modimp reads and
-// modexp writes; record index = element index.  The kernels of such a chain are in the section "byte records" below; with both 0 none of
-// them is compiled, BArgs stays on the host and k_chain is launched as it always was.
+// modexp writes (little-endian, or with the top bit a sign, where the unit says so per array: below); record index = element index.
+// The kernels of such a chain are in the section "byte records" below; with both 0 none of them is compiled, BArgs stays on the host
+// and k_chain is launched as it always was.
 #ifndef CHAIN_NBIN
 #define CHAIN_NBIN 0
 #endif
@@ -116,7 +120,33 @@ __global__ __launch_bounds__(CBLOCK) CHAIN_KERNEL_ATTR void k_chain(Args A, size
 //            barriers (the CHAIN_AOS_IMAGES rule); the outputs go through the first image.
 // Which of the two a call on aligned arrays takes is BYTES_STAGED below (measured: tools/chain_bytes_rate.py, docs/fused_chains.md);
 // the environment variable MA_CHAIN_BYTES=staged|direct, read at every call, overrides it (tests, the rate tool).
+// Byte order and sign are properties of each byte array, fixed when the unit is emitted: CHAIN_BIN_LE / CHAIN_BOUT_LE name the arrays
+// whose records are least significant byte first (load_le_record / store_le_record: no bswap, word order kept); CHAIN_BIN_SIGN /
+// CHAIN_BOUT_SIGN those whose most significant bit -- bit 8 NBYTES - 1 of the integer, the top bit of the record's last byte where it is
+// little-endian and of its first where it is big-endian -- is not part of the value (RFC 8032's x_0, the bit rfc7748.c:172 masks).  The
+// bit is taken out of, or OR-ed into, the words in registers, between the load and limbs_from_words and between words_from_limbs and
+// the store.  The array index reaches these helpers as a literal of chain_step: the tests fold.  A unit that defines none of the four
+// compiles the text it always did.
 constexpr int NW = Field<P>::NW;
+constexpr int TOPW = (8 * NB - 1) / 64, TOPB = (8 * NB - 1) % 64;     // where a record's most significant bit lies in its words
+MA_DEV void load_record(int j, const unsigned char* bytes, size_t t, word_t* w) {
+#ifdef CHAIN_BIN_LE
+    if ((CHAIN_BIN_LE >> j) & 1) { load_le_record<P>(bytes, t, w); return; }
+#endif
+    load_be_record<P>(bytes, t, w);
+}
+MA_DEV void store_record(int k, unsigned char* bytes, size_t t, const word_t* w) {
+#ifdef CHAIN_BOUT_LE
+    if ((CHAIN_BOUT_LE >> k) & 1) { store_le_record<P>(bytes, t, w); return; }
+#endif
+    store_be_record<P>(bytes, t, w);
+}
+MA_DEV int take_sign(word_t* w) {
+    const int s = (int)((w[TOPW] >> TOPB) & 1);
+    w[TOPW] &= ~((word_t)1 << TOPB);
+    return s;
+}
+MA_DEV void put_sign(word_t* w, int d) { w[TOPW] |= (word_t)(unsigned)d << TOPB; }       // (defined for d = 0 / 1)
 constexpr bool BYTES_STAGED = CHAIN_BYTES_STAGED; // the path of a call on 16-byte aligned record arrays: the unit says (fuse.BYTES_IO_DEFAULT)
 MA_DEV int imp_words(const word_t* w, spint* v) {
     Field<P>::limbs_from_words(w, v);
@@ -128,17 +158,37 @@ template <int EPT> struct ByteIO : SoaIO<EPT> {       // direct: records EPT t .
     MA_DEV void imp(int j, spint (*v)[P::N], int* s) const {
         static_for<0, EPT>([&](auto E) {
             word_t w[NW];
-            load_be_record<P>(B.bin[j], (size_t)EPT * this->t + E, w);
+            load_record(j, B.bin[j], (size_t)EPT * this->t + E, w);
             s[E] = imp_words(w, v[E]);
         });
     }
+#ifdef CHAIN_BIN_SIGN
+    MA_DEV void imp(int j, spint (*v)[P::N], int* s, int* sign) const {
+        static_for<0, EPT>([&](auto E) {
+            word_t w[NW];
+            load_record(j, B.bin[j], (size_t)EPT * this->t + E, w);
+            sign[E] = take_sign(w);
+            s[E] = imp_words(w, v[E]);
+        });
+    }
+#endif
     MA_DEV void exp(int k, spint (*v)[P::N]) const {
         static_for<0, EPT>([&](auto E) {
             word_t w[NW];
             Field<P>::words_from_limbs(v[E], w);
-            store_be_record<P>(B.bout[k], (size_t)EPT * this->t + E, w);
+            store_record(k, B.bout[k], (size_t)EPT * this->t + E, w);
         });
     }
+#ifdef CHAIN_BOUT_SIGN
+    MA_DEV void exp(int k, spint (*v)[P::N], const int* sign) const {
+        static_for<0, EPT>([&](auto E) {
+            word_t w[NW];
+            Field<P>::words_from_limbs(v[E], w);
+            put_sign(w, sign[E]);
+            store_record(k, B.bout[k], (size_t)EPT * this->t + E, w);
+        });
+    }
+#endif
 };
 template <int EPT>
 __global__ __launch_bounds__(CBLOCK) CHAIN_KERNEL_ATTR void k_chain_direct(Args A, BArgs B, size_t nthreads, Ld L) {
@@ -204,7 +254,7 @@ template <int EPT> struct StagedIO {
     MA_DEV void sel(int k, int* s) const { static_for<0, EPT>([&](auto E) { s[E] = live() ? A.sel[k][(size_t)EPT * t() + E] : 0; }); }
     MA_DEV void store(int k, spint (*v)[P::N]) const { if (live()) store_soa<P, EPT>(A.out[k], L, t(), v); }
     MA_DEV void pred(int k, const int* s) const { static_for<0, EPT>([&](auto E) { if (live()) A.pred[k][(size_t)EPT * t() + E] = s[E]; }); }
-    MA_DEV void imp(int j, spint (*v)[P::N], int* s) const {
+    MA_DEV unsigned char* image_in(int j) const {         // the image that holds this workgroup's records of byte input j
         unsigned char* img = sh;
         if constexpr (images(EPT) == CHAIN_NBIN) {
             img += j * image_bytes(EPT);                  // (k_chain_staged has filled the images)
@@ -213,23 +263,52 @@ template <int EPT> struct StagedIO {
             stage_in(B.bin[j] + first(), cnt * EPT * NB, img);
             __syncthreads();
         }
+        return img;
+    }
+    MA_DEV void imp(int j, spint (*v)[P::N], int* s) const {
+        unsigned char* img = image_in(j);
         static_for<0, EPT>([&](auto E) {
             word_t w[NW];
-            if (live()) load_be_record<P>(mine(img, E), 0, w);
+            if (live()) load_record(j, mine(img, E), 0, w);
             else static_for<0, NW>([&](auto K) { w[K] = 0; });
             s[E] = imp_words(w, v[E]);
         });
     }
+#ifdef CHAIN_BIN_SIGN
+    MA_DEV void imp(int j, spint (*v)[P::N], int* s, int* sign) const {
+        unsigned char* img = image_in(j);
+        static_for<0, EPT>([&](auto E) {
+            word_t w[NW];
+            if (live()) load_record(j, mine(img, E), 0, w);
+            else static_for<0, NW>([&](auto K) { w[K] = 0; });
+            sign[E] = take_sign(w);
+            s[E] = imp_words(w, v[E]);
+        });
+    }
+#endif
     MA_DEV void exp(int k, spint (*v)[P::N]) const {
         __syncthreads();
         static_for<0, EPT>([&](auto E) {
             word_t w[NW];
             Field<P>::words_from_limbs(v[E], w);
-            if (live()) store_be_record<P>(mine(sh, E), 0, w);
+            if (live()) store_record(k, mine(sh, E), 0, w);
         });
         __syncthreads();
         stage_out(B.bout[k] + first(), cnt * EPT * NB, sh);
     }
+#ifdef CHAIN_BOUT_SIGN
+    MA_DEV void exp(int k, spint (*v)[P::N], const int* sign) const {
+        __syncthreads();
+        static_for<0, EPT>([&](auto E) {
+            word_t w[NW];
+            Field<P>::words_from_limbs(v[E], w);
+            put_sign(w, sign[E]);
+            if (live()) store_record(k, mine(sh, E), 0, w);
+        });
+        __syncthreads();
+        stage_out(B.bout[k] + first(), cnt * EPT * NB, sh);
+    }
+#endif
 };
 // the loop is on the workgroup's base lane: block-uniform, since barriers sit inside it
 template <int EPT>

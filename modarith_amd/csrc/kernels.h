@@ -639,6 +639,38 @@ __device__ __forceinline__ void store_be_record(unsigned char* bytes, size_t t, 
         });
     }
 }
+// The same records least significant byte first (the RFC 7748 / RFC 8032 wire formats; what the reference's reverse() makes of them
+// before modimp): word k of the integer is chunk k as it lies in memory, no swap and no reversal of the word order; bytes are
+// assembled one by one where NBYTES is no multiple of 8, at word length 32 through the opaque form of load_be_record -- the same
+// source pattern, open to the same fold.  Used by the fused chains (csrc/chain.inc)
+template <class P>
+__device__ __forceinline__ void load_le_record(const unsigned char* bytes, size_t t, word_t* w) {
+    constexpr int NW = Field<P>::NW, NB = P::NBYTES;
+    if constexpr (NB % 8 == 0) {
+        const word_t* src = reinterpret_cast<const word_t*>(bytes) + t * NW;
+        static_for<0, NW>([&](auto K) { w[K] = src[K]; });
+    } else {
+        const unsigned char* src = bytes + t * NB;
+        static_for<0, NW>([&](auto K) { w[K] = 0; });
+        static_for<0, NB>([&](auto B) {
+            constexpr int pos = B;                          // byte significance (0 = least)
+            uint32_t by = src[B];
+            if constexpr (MA_WL == 32) asm volatile("" : "+v"(by));
+            w[pos / 8] |= (word_t)by << (8 * (pos % 8));
+        });
+    }
+}
+template <class P>
+__device__ __forceinline__ void store_le_record(unsigned char* bytes, size_t t, const word_t* w) {
+    constexpr int NW = Field<P>::NW, NB = P::NBYTES;
+    if constexpr (NB % 8 == 0) {
+        word_t* dst = reinterpret_cast<word_t*>(bytes) + t * NW;
+        static_for<0, NW>([&](auto K) { dst[K] = w[K]; });
+    } else {
+        unsigned char* dst = bytes + t * NB;
+        static_for<0, NB>([&](auto B) { dst[B] = (unsigned char)(w[B / 8] >> (8 * (B % 8))); });
+    }
+}
 template <class P>
 __global__ __launch_bounds__(BLOCK) void k_imp(const unsigned char* bytes, spint* a, int* flag, size_t n, Ld ld) {
     for (size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x; t < n; t += (size_t)gridDim.x * BLOCK) {

@@ -50,9 +50,19 @@ below p); `ch.output_bytes(v)` is a byte-record output, modexp(v).  modimp and m
 moves 96 bytes an element over X25519 where the four calls move 344.  Records are 8-byte aligned where Nbytes is a multiple of 8 (the
 rule of modimp_<P>_batch) and may be anywhere otherwise; a byte output may be the array of a byte input.  A chain needs at least one element batch or one byte input: without
 element arrays on either side `ld` is ignored.  There is no element-major entry for such a chain (`_aos` refuses).  `pubkey_chain()` below
-checks an uncompressed P-256 public key as it arrives, 64 bytes in and 4 out.  Out of scope: little-endian records (the RFC 7748 / RFC 8032
-wire formats: the reference reverses them on the host), taking a sign bit out of a record, modshl / modshr / mod2r.  docs/fused_chains.md,
-"Chains that speak bytes", has the kernels' two ways to the bytes and their rates.
+checks an uncompressed P-256 public key as it arrives, 64 bytes in and 4 out.  docs/fused_chains.md, "Chains that speak bytes", has the
+kernels' two ways to the bytes and their rates.
+
+Records may be little-endian and carry a sign: `ch.input_bytes(little=True)` reads records least significant byte first (the RFC 7748 /
+RFC 8032 wire formats, which the reference reverses on the host), `ch.input_bytes(sign=True)` returns (v, ok, s) with s the record's most
+significant bit as an int of the chain, cleared before modfsb sees the integer (rfc7748.c:172's mask, RFC 8032's x_0);
+`ch.output_bytes(v, little=True, sign=d)` writes such records, d << 7 OR-ed into the most significant byte.  Byte order and sign are
+compile-time properties of each array (CHAIN_BIN_LE / CHAIN_BIN_SIGN / CHAIN_BOUT_LE / CHAIN_BOUT_SIGN, emitted only by a chain that
+uses them); the bit moves in registers.  `rfc8032_decode_chain()`, `rfc8032_encode_chain()` and `edwards_to_montgomery_chain()` below are
+written with them.  The rest of field.c: `ch.modshl(a, k)`, `v, r = ch.modshr(a, k)` (r: the bits shifted out), `ch.mod2r(r)`,
+`v, f = ch.modfsb(a)`, `v, f = ch.flatten(a)`; modshl leaves the limb contract, so a 64-bit chain with one runs the exact products.
+Out of scope: the 57-byte records of Ed448 (a record is Nbytes long), and prop, which is static.  docs/fused_chains.md, "Little-endian
+records and sign bits" and "The rest of field.c".
 
 Word length 32: `Chain(prime, name, wl=32)` is the same chain over the 32-bit word form of X25519, NIST256 and X448 (csrc/kernels32.h,
 namespace ma32; int32 batches of `Field(prime, wl=32)`): what a port of the reference's per-thread CUDA form (simd/pseudo_cuda.py 32)
@@ -79,17 +89,21 @@ _NAME_RE = re.compile(r"^[A-Za-z][A-Za-z0-9_]*$")
 # op -> (Field<P> function, operand count, takes an int immediate)
 _OPS = {"modmul": 2, "modadd": 2, "modsub": 2, "modsqr": 1, "modneg": 1, "nres": 1, "redc": 1, "modcpy": 1, "modinv": 1, "modmli": 1,
         "modadd_lazy": 2, "modsub_lazy": 2, "modneg_lazy": 1, "modnsqr": 1, "modpro": 1, "modsqrt": 1, "modhaf": 1, "modcmv": 2, "modcsw": 2,
-        "modint": 0, "modone": 0, "modzer": 0,
+        "modint": 0, "modone": 0, "modzer": 0, "modshl": 1, "modshr": 1, "mod2r": 0, "modfsb": 1, "flatten": 1,
         "modis0": 1, "modis1": 1, "modsign": 1, "modcmp": 2, "modqr": 1, "lnot": 0, "land": 0, "lor": 0, "lxor": 0}
 _HEAVY = ("modinv", "modpro", "modsqrt", "modqr")  # long exponentiation chains: one element per lane
 _PREDS = ("modis0", "modis1", "modsign", "modcmp", "modqr")      # Field<P> functions that return an int: the result is a Pred
 _INT_OPS = ("lnot", "land", "lor", "lxor")        # the plain C the reference writes on its 0/1 ints
+_INT_RET = ("modshr", "modfsb", "flatten")        # in-place functions of field.c that return an int beside the element they leave: Op.sdst
 # an operation as a line of body<F>, over the fields of its Op (h: the progenitor b, or nullptr); the rest: F::op(operands, result), by operand count
 _CALLS = {"modcsw": "F::modcpy(v{a}, v{dst}); F::modcpy(v{b}, v{dst2}); F::modcsw(s{sa}, v{dst}, v{dst2});",
           "modcmv": "F::modcpy(v{b}, v{dst}); F::modcmv(s{sa}, v{a}, v{dst});",
           "modnsqr": "F::modcpy(v{a}, v{dst}); F::modnsqr(v{dst}, {imm});", "modhaf": "F::modcpy(v{a}, v{dst}); F::modhaf(v{dst});",
           "modsqrt": "F::modsqrt(v{a}, {h}, v{dst});", "modinv": "F::modinv(v{a}, {h}, v{dst}); inv_normalise<F>(v{dst});",
           "modqr": "s{dst} = F::modqr({h}, v{a});", "modmli": "F::modmli(v{a}, {imm}, v{dst});", "modint": "F::modint({imm}, v{dst});",
+          "modshl": "F::modcpy(v{a}, v{dst}); F::modshl({imm}, v{dst});", "modshr": "F::modcpy(v{a}, v{dst}); s{sdst} = F::modshr({imm}, v{dst});",
+          "mod2r": "F::mod2r({imm}, v{dst});", "modfsb": "F::modcpy(v{a}, v{dst}); s{sdst} = (int)F::modfsb(v{dst});",
+          "flatten": "F::modcpy(v{a}, v{dst}); s{sdst} = (int)F::flatten(v{dst});",
           "lnot": "s{dst} = 1 - s{sa};", "land": "s{dst} = s{sa} & s{sb};", "lor": "s{dst} = s{sa} | s{sb};", "lxor": "s{dst} = s{sa} ^ s{sb};",
           0: "F::{op}(v{dst});", 1: "F::{op}(v{a}, v{dst});", 2: "F::{op}(v{a}, v{b}, v{dst});"}
 _WITH_H = ("modinv", "modsqrt", "modqr")          # take an optional progenitor h = modpro(a)
@@ -137,8 +151,25 @@ class Op(NamedTuple):
     b: int = -1
     sa: int = -1            # int operands: of lnot / land / lor / lxor, and sa the selector of modcmv / modcsw
     sb: int = -1
-    imm: int = 0            # the C int of modmli / modint / modnsqr
+    imm: int = 0            # the C int of modmli / modint / modnsqr / modshl / modshr / mod2r
     dst2: int = -1          # modcsw: the second value it defines
+    sdst: int = -1          # modshr / modfsb / flatten: the int they return, beside the value dst
+
+
+class BIn(NamedTuple):
+    """one byte-record input"""
+    v: int                  # the value modimp leaves
+    ok: int                 # modimp's return value: its place among the computed ints
+    little: bool = False    # byte 0 of a record is the least significant
+    sign: int = -1          # the record's top bit, taken out of the integer: its place among the computed ints; -1 = the bit is part of the value
+
+
+class BOut(NamedTuple):
+    """one byte-record output"""
+    v: int                  # the value
+    t: int                  # the value that holds its redc
+    little: bool = False
+    sign: int = -1          # the int (of the int space) OR-ed into the record's top bit; -1 = none
 
 
 class Chain:
@@ -166,8 +197,8 @@ class Chain:
         self.npred = 0                      # ints computed inside the chain (Pred): s<nsel> .. s<nsel + npred - 1>
         self.pouts: List[int] = []          # the ints that are outputs (indices of the int space), in the order of out[] after the element outputs
         self.nvals = 0
-        self.bins: List[tuple] = []         # byte-record inputs: (the value modimp leaves, its flag's place among the computed ints), in the order of in[]
-        self.bouts: List[tuple] = []        # byte-record outputs: (the value, the value that holds its redc), in the order of out[]
+        self.bins: List[BIn] = []           # byte-record inputs, in the order of in[]
+        self.bouts: List[BOut] = []         # byte-record outputs, in the order of out[]
 
     # ------------------------------------------------------------------ building
     def _new(self) -> Val:
@@ -176,7 +207,7 @@ class Chain:
         return v
 
     def _declaring(self) -> None:                     # every kind of input: the ints' places (selectors first) and the vote rest on it
-        if self.ops:
+        if self.ops or any(b.sign >= 0 for b in self.bouts):     # (a byte output with a sign has fixed that int's place)
             raise ValueError("declare every input before the first operation")
 
     def _room(self) -> None:                          # every operation
@@ -212,21 +243,32 @@ class Chain:
     def nshared(self) -> int:
         return len(self.sh_idx)
 
-    def input_bytes(self):
-        """a byte-record input: n records of Nbytes big-endian bytes.  Returns (v, ok): v is what
-        Field.modimp leaves (the integer the bytes spell, modfsb, nres), ok its return value as a Pred: 1 where the integer was below p"""
+    def input_bytes(self, little: bool = False, sign: bool = False):
+        """a byte-record input: n records of Nbytes bytes, big-endian, or with little=True least significant byte first (the integer that
+        reverse() + modimp would read).  Returns (v, ok): v is what Field.modimp leaves (the integer the bytes spell, modfsb, nres), ok its
+        return value as a Pred: 1 where the integer was below p.  With sign=True returns (v, ok, s): s is the record's most significant
+        bit -- bit 8 Nbytes - 1 of the integer -- as an int of the chain, and the bit is cleared before modfsb / nres see the integer
+        (rfc7748.c:172's mask, RFC 8032's x_0).  Where 8 Nbytes == Nbits that is simply the value's top bit"""
         self._declaring()
         v, ok = self._new(), Pred(self, self.npred)
         self.npred += 1
-        self.bins.append((v.idx, ok.idx))
-        return v, ok
+        s = None
+        if sign:
+            s = Pred(self, self.npred)
+            self.npred += 1
+        self.bins.append(BIn(v.idx, ok.idx, bool(little), s.idx if sign else -1))
+        return (v, ok, s) if sign else (v, ok)
 
-    def output_bytes(self, v: Val) -> None:
-        """a byte-record output, modexp(v): redc, then Nbytes big-endian bytes a record"""
+    def output_bytes(self, v: Val, little: bool = False, sign=None) -> None:
+        """a byte-record output, modexp(v): redc, then Nbytes bytes a record, big-endian or with little=True least significant byte first.
+        sign=d, a Pred or Sel of this chain, ORs d << 7 into the record's most significant byte (`pub[56] = (char)(sign << 7)`): defined
+        for d = 0 / 1"""
         self._own(v)
         if v.idx in self.sh_idx:
             raise ValueError("a shared operand is not a per-element array: output_bytes modcpy() of it")
-        self.bouts.append((v.idx, self._new().idx))
+        if sign is not None and (not isinstance(sign, (Sel, Pred)) or sign.chain is not self):
+            raise ValueError("the sign of a byte output is an int of this chain: a predicate, a selector, the sign of a byte input")
+        self.bouts.append(BOut(v.idx, self._new().idx, bool(little), self._sel(sign) if sign is not None else -1))
 
     def inputs(self, k: int) -> List[Val]:
         return [self.input() for _ in range(k)]
@@ -266,6 +308,44 @@ class Chain:
         if isinstance(k, bool) or not isinstance(k, int) or not -(1 << 31) <= k < (1 << 31):
             raise ValueError("modint takes a C int")
         return self._op("modint", None, imm=k)
+
+    def mod2r(self, r: int):
+        """the constant 2^r as Field<P>::mod2r makes it (Montgomery form included; zero for r >= 8 Nbytes, as there)"""
+        if isinstance(r, bool) or not isinstance(r, int) or not 0 <= r < (1 << 31):
+            raise ValueError("mod2r takes an unsigned C int")
+        return self._op("mod2r", None, imm=r)
+
+    # field.c's shifts by less than a limb, and the functions that return an int beside the element they leave in place
+    def _shift(self, k):
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= min(self.params.radix - 1, 31):
+            raise ValueError("a shift count is a C immediate with 1 <= k < Radix (%d) and k <= 31 (got %r)" % (self.params.radix, k))
+        return k
+
+    def modshl(self, a, k: int):
+        """a << k on the limbs (field.c's modshl: no reduction -- the top limb grows by k bits, so a 64-bit chain with a modshl runs the
+        exact products throughout)"""
+        return self._op("modshl", a, imm=self._shift(k))
+
+    def _with_int(self, op: str, a: Val, imm: int = 0):
+        self._own(a)
+        self._room()
+        d, r = self._new(), Pred(self, self.npred)
+        self.npred += 1
+        self.ops.append(Op(op, d.idx, a.idx, imm=imm, sdst=self.nsel + r.idx))
+        return d, r
+
+    def modshr(self, a, k: int):
+        """(a >> k, r): r the k bits shifted out, field.c's return value -- an int32 output like any other; as a selector or an operand of
+        land / lor / lxor / lnot it is defined for 0 / 1 only, i.e. k = 1 (as the reference's own expressions are)"""
+        return self._with_int("modshr", a, self._shift(k))
+
+    def modfsb(self, a):
+        """(the canonical limbs of a - p or, where that is negative, of a; 1 where a was below p): field.c's modfsb"""
+        return self._with_int("modfsb", a)
+
+    def flatten(self, a):
+        """(a with its carries propagated, plus p where it was negative; that carry): field.c's flatten"""
+        return self._with_int("flatten", a)
 
     def modone(self): return self._op("modone", None)
     def modzer(self): return self._op("modzer", None)
@@ -391,9 +471,13 @@ class Chain:
     def unfused_traffic_bytes(self) -> int:
         """a predicate call reads its operand arrays and writes 4 bytes; a selector, streamed in or computed, is a 4-byte read of the call that
         uses it; a progenitor passed as h is one more operand array.  The int expressions are not counted (a caller's own elementwise passes).
-        A byte input is a modimp call (Nbytes in, an element and the 4-byte flag out), a byte output a modexp call"""
+        A byte input is a modimp call (Nbytes in, an element and the 4-byte flag out), a byte output a modexp call; a little-endian record
+        costs one more read and write of Nbytes (the reversal), a sign on either side 4 bytes (its own int array).  modshr / modfsb /
+        flatten write their 4-byte int"""
         w = (self.wl // 8) * self.params.nlimbs
         total = len(self.bins) * (self.params.nbytes + w + 4) + len(self.bouts) * (w + self.params.nbytes)
+        recs = self.bins + self.bouts
+        total += 2 * self.params.nbytes * sum(r.little for r in recs) + 4 * sum(r.sign >= 0 for r in recs)
         for o in self.ops:
             op = o.op
             if op in _INT_OPS:
@@ -402,12 +486,12 @@ class Chain:
             if op in _PREDS:
                 total += w * arrays + 4
             else:
-                total += w * (arrays + (2 if op == "modcsw" else 1)) + (4 if op in ("modcmv", "modcsw") else 0)
+                total += w * (arrays + (2 if op == "modcsw" else 1)) + (4 if op in ("modcmv", "modcsw") + _INT_RET else 0)
         return total
 
     def _body_lines(self) -> List[str]:
         """the chain as Field<P> calls on registers, one line per operation"""
-        L = ["    F::nres(v%d, v%d);" % (i, i) for i, _ in self.bins]      # io.imp() left the canonical limbs: the rest of modimp, on the voted products
+        L = ["    F::nres(v%d, v%d);" % (i, i) for i in (b.v for b in self.bins)]      # io.imp() left the canonical limbs: the rest of modimp, on the voted products
         tested = set()                                        # values a predicate has read
         for o in self.ops:
             op, d, a, b = o.op, o.dst, o.a, o.b
@@ -426,7 +510,7 @@ class Chain:
                 L.append("    %ss%d = F::%s(%s);" % (pre, d, op, ", ".join(x for x in ab if x != -1)))
                 continue
             L.append("    " + _CALLS.get(op, _CALLS[_OPS[op]]).format(h="nullptr" if b < 0 else "v%d" % b, **o._asdict()))
-        return L + ["    F::redc(v%d, v%d);" % (a, d) for a, d in self.bouts]            # the first half of modexp; io.exp() makes the bytes
+        return L + ["    F::redc(v%d, v%d);" % (a, d) for a, d in ((b.v, b.t) for b in self.bouts)]            # the first half of modexp; io.exp() makes the bytes
 
     # The unit, piece by piece; every helper returns lines, source() puts them in order
     def _shape(self, ept, policy, block):
@@ -466,12 +550,20 @@ class Chain:
         if self.pouts:
             L.append("#define CHAIN_NPRED %d   // int32 results, one entry per element: device arrays after the element outputs in out[]" % len(self.pouts))
         if self.bins:
-            L.append("#define CHAIN_NBIN %d   // byte-record inputs: arrays of n records of P::NBYTES big-endian bytes after the element batches in in[]" % len(self.bins))
+            L.append("#define CHAIN_NBIN %d   // byte-record inputs: arrays of n records of P::NBYTES %s after the element batches in in[]"
+                     % (len(self.bins), "bytes (byte order and sign: below)" if any(b.little or b.sign >= 0 for b in self.bins) else "big-endian bytes"))
         if self.bins or self.bouts:
             L.append("#define CHAIN_BYTES_STAGED %d   // the way to the bytes of a call on 16-byte aligned record arrays: 1 = staged through LDS, 0 = direct (fuse.BYTES_IO_DEFAULT)"
                      % (BYTES_IO_DEFAULT[self.wl] == "staged"))
         if self.bouts:
             L.append("#define CHAIN_NBOUT %d   // byte-record outputs: arrays of n records after the element outputs in out[]" % len(self.bouts))
+        for what, recs in (("BIN", self.bins), ("BOUT", self.bouts)):      # (per-array bitmasks; a chain of big-endian records without signs names none)
+            le, sg = (sum(1 << k for k, r in enumerate(recs) if on(r)) for on in (lambda r: r.little, lambda r: r.sign >= 0))
+            if le:
+                L.append("#define CHAIN_%s_LE 0x%x   // bit j: the records of byte %s j are little-endian (byte 0 the least significant)" % (what, le, "input" if what == "BIN" else "output"))
+            if sg:
+                L.append("#define CHAIN_%s_SIGN 0x%x   // bit j: the most significant bit of the records of byte %s j is a sign, %s" % (
+                    what, sg, "input" if what == "BIN" else "output", "taken out before modfsb" if what == "BIN" else "OR-ed in after redc"))
         if waves:
             L.append("#define CHAIN_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(%d, %d)))" % (waves, waves))
         return L
@@ -495,12 +587,13 @@ class Chain:
         if self.wl == 32:
             return ["    static_for<0, EPT>([&](auto E) { body<Field<P>>(%s); });" % args]
         # modint of a negative int is the word (spint)k, outside the limb contract at 64 bits: such a chain runs the exact products, as Field.modint does
-        if policy == "vote" and any(o.op == "modint" and o.imm < 0 for o in self.ops):
+        # modshl does not reduce: the top limb of its result grows by k bits and leaves the contract in the same way
+        if policy == "vote" and any((o.op == "modint" and o.imm < 0) or o.op == "modshl" for o in self.ops):
             policy = "exact"
         return ["    bool fast = %s;" % ("true" if policy == "fast" else "false"),
                 "    if constexpr (P::SPLIT > 0 && %s) {" % ("true" if policy == "vote" else "false"),
                 "        bool ok = %s;" % (" && ".join("in_split_contract<P>(v%d)" % i for i in self.sh_idx) or "true"),
-                "        static_for<0, EPT>([&](auto E) { ok = ok && " + " && ".join("in_split_contract<P>(v%d[E])" % i for i in self.in_idx + [b[0] for b in self.bins]) + "; });",
+                "        static_for<0, EPT>([&](auto E) { ok = ok && " + " && ".join("in_split_contract<P>(v%d[E])" % i for i in self.in_idx + [b.v for b in self.bins]) + "; });",
                 "        fast = __all(ok);",
                 "    }",
                 "    if (fast) {",
@@ -518,10 +611,10 @@ class Chain:
         L += ["    const spint* v%d = io.shared(%d);" % (i, k) for k, i in enumerate(self.sh_idx)]
         L += ["    int s%d[EPT]; io.sel(%d, s%d);" % (k, k, k) for k in range(self.nsel)]
         L += ["    int s%d[EPT];" % (self.nsel + k) for k in range(self.npred)]
-        L += ["    io.imp(%d, v%d, s%d);" % (k, i, self.nsel + f) for k, (i, f) in enumerate(self.bins)]
+        L += ["    io.imp(%d, v%d, s%d%s);" % (k, b.v, self.nsel + b.ok, ", s%d" % (self.nsel + b.sign) if b.sign >= 0 else "") for k, b in enumerate(self.bins)]
         L += self._vote(policy)
         L += ["    io.store(%d, v%d);" % (k, o) for k, o in enumerate(self.outs)]
-        L += ["    io.exp(%d, v%d);" % (k, t) for k, (_, t) in enumerate(self.bouts)]
+        L += ["    io.exp(%d, v%d%s);" % (k, b.t, ", s%d" % b.sign if b.sign >= 0 else "") for k, b in enumerate(self.bouts)]
         L += ["    io.pred(%d, s%d);" % (k, o) for k, o in enumerate(self.pouts)]
         return L + ["}"]
 
@@ -773,14 +866,26 @@ def decompress_chain(curve: str = "ED25519", wl: int = 64, name: str = "decompre
     with no x turned into the point at infinity (0, 1, 1) by modcmv instead of the reference's early return.
     Returns (chain, [limbs of d]); f(y, d, s) -> (x, y, z, ok), ok = the modqr test: 1 - isinf of the point (for y = 1, whose x is 0, the
     point that was asked for IS the neutral element: ok = 1)"""
-    from .curves import curve as _curve
-    c = _curve(curve)
-    if c.a != -1 or c.small_b:
-        raise ValueError("decompress_chain is written for a = -1 and a full-size d (ED25519; got %s)" % curve)
+    c = _edwards(curve, "decompress_chain")
     ch = Chain(c.field, name, wl=wl)
     y = ch.input()
     d = ch.shared()
     s = ch.selector()
+    _decompress(ch, y, d, s)
+    return ch, [internal_limbs(c.field, c.d, wl)]
+
+
+def _edwards(curve: str, what: str):
+    from .curves import curve as _curve
+    c = _curve(curve)
+    if c.a != -1 or c.small_b:
+        raise ValueError("%s is written for a = -1 and a full-size d (ED25519; got %s)" % (what, curve))
+    return c
+
+
+def _decompress(ch: Chain, y, d, s, valid=None) -> None:
+    """the body and the outputs of decompress_chain() on a chain whose inputs are declared: y, the shared d, the int s; valid: an int
+    that must be 1 beside the modqr test for the point to stand (the flag of a byte input)"""
     one = ch.modone()
     Y = ch.modsqr(y)
     U = ch.modsub(one, Y)                                   # 1 - y^2
@@ -789,6 +894,8 @@ def decompress_chain(curve: str = "ED25519", wl: int = 64, name: str = "decompre
     W = ch.modmul(ch.modmul(U, O), V)                       # U^3 V
     H = ch.modpro(W)
     ok = ch.modqr(W, H)
+    if valid is not None:
+        ok = ch.land(valid, ok)
     R = ch.modsqrt(W, H)
     X = ch.modmul(ch.modmul(ch.modinv(W, H), R), O)
     X = ch.modcmv(ch.lxor(ch.modsign(X), s), ch.modneg(X), X)        # (modsign(U) - s) & 1 on 0/1 ints
@@ -797,7 +904,42 @@ def decompress_chain(curve: str = "ED25519", wl: int = 64, name: str = "decompre
     ch.output(ch.modcmv(bad, one, y))
     ch.output(ch.modcpy(one))
     ch.output(ok)
+
+
+def rfc8032_decode_chain(curve: str = "ED25519", wl: int = 64, name: str = "rfc8032_decode"):
+    """RFC 8032 5.1.3 as one kernel: ONE little-endian record with the sign of x in its top bit in, the point out -- decompress_chain()'s
+    body on the y and the sign that the record holds, with ok = flag(y) & modqr(...): a record whose y has no x, or whose y is not below
+    p, gives (0, 1, 1) and ok = 0.  32 bytes in, three element arrays and 4 bytes out.
+    Returns (chain, [limbs of d]); f(record, d) -> (x, y, z, ok)"""
+    c = _edwards(curve, "rfc8032_decode_chain")
+    ch = Chain(c.field, name, wl=wl)
+    y, fy, s = ch.input_bytes(little=True, sign=True)
+    d = ch.shared()
+    _decompress(ch, y, d, s, valid=fy)
     return ch, [internal_limbs(c.field, c.d, wl)]
+
+
+def rfc8032_encode_chain(curve: str = "ED25519", wl: int = 64, name: str = "rfc8032_encode"):
+    """RFC 8032 5.1.2: affine x, y element batches in, ONE record out -- y little-endian with modsign(x) in the top bit (ecnXXXget, reverse
+    and `sign << 7` of the reference's callers).  Returns the chain; f(x, y) -> (record,)"""
+    c = _edwards(curve, "rfc8032_encode_chain")
+    ch = Chain(c.field, name, wl=wl)
+    x, y = ch.inputs(2)
+    ch.output_bytes(y, little=True, sign=ch.modsign(x))
+    return ch
+
+
+def edwards_to_montgomery_chain(curve: str = "ED25519", wl: int = 64, name: str = "ed_to_mont"):
+    """RFC 7748 4.1, the birational map on wire values: a little-endian record of an Edwards y (the sign bit ignored) in, the
+    little-endian record of u = (1 + y) / (1 - y) and ok = flag(y) out.  Bytes on both sides; one inversion (modinv of 0 is 0: y = 1 gives
+    u = 0).  Returns the chain; f(record) -> (record, ok)"""
+    c = _edwards(curve, "edwards_to_montgomery_chain")
+    ch = Chain(c.field, name, wl=wl)
+    y, fy, _ = ch.input_bytes(little=True, sign=True)
+    one = ch.modone()
+    ch.output_bytes(ch.modmul(ch.modadd(one, y), ch.modinv(ch.modsub(one, y))), little=True)
+    ch.output(fy)
+    return ch
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -813,10 +955,13 @@ def parse(prime: str, name: str, text: str, wl: int = 64) -> Chain:
     ints and selectors (0 / 1; `not` binds loosest: write `d & (not e)`); modsqrt(a, h), modinv(a, h), modqr(x, h) take the progenitor as
     an optional second argument; `out` takes ints as well: int32 results after the element results.
     `bytes a, b` declares byte-record inputs (a is what modimp leaves), `flag(a)` is modimp's return value for that input, an int like the
-    predicates', and `outbytes expr, ...` outputs modexp of the expressions as byte records."""
+    predicates', and `outbytes expr, ...` outputs modexp of the expressions as byte records.
+    `lebytes a` declares little-endian records, `sbytes a` / `lesbytes a` records whose top bit is taken out as `sign(a)`, an int beside
+    `flag(a)`; `outlebytes expr, ...` writes little-endian records, `outsbytes (expr, int_expr), ...` / `outlesbytes (expr, int_expr), ...`
+    records with the int in their top bit.  `v, r = modshr(a, 1)`, `v, f = modfsb(a)` and `v, f = flatten(a)` assign both results."""
     import ast
     ch = Chain(prime, name, wl)
-    env, flags = {}, {}
+    env, flags, signs = {}, {}, {}
     _INT_AST = {ast.BitAnd: "land", ast.BitOr: "lor", ast.BitXor: "lxor"}
 
     def ev(node):
@@ -836,6 +981,10 @@ def parse(prime: str, name: str, text: str, wl: int = 64) -> Chain:
             if len(node.args) != 1 or not isinstance(node.args[0], ast.Name) or node.args[0].id not in flags:
                 raise ValueError("flag() takes the name of a byte input: %r" % ast.unparse(node))
             return flags[node.args[0].id]
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id == "sign" and not node.keywords:
+            if len(node.args) != 1 or not isinstance(node.args[0], ast.Name) or node.args[0].id not in signs:
+                raise ValueError("sign() takes the name of a byte input declared with sbytes or lesbytes: %r" % ast.unparse(node))
+            return signs[node.args[0].id]
         if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and not node.keywords:
             fn = node.func.id
             if fn not in _OPS or not hasattr(ch, fn):
@@ -843,18 +992,28 @@ def parse(prime: str, name: str, text: str, wl: int = 64) -> Chain:
             return getattr(ch, fn)(*[ev(a) for a in node.args])
         raise ValueError("cannot parse %r" % ast.unparse(node))
 
-    declare = {"in": ch.input, "shared": ch.shared, "sel": ch.selector, "bytes": ch.input_bytes}
-    emit_as = {"out": ch.output, "outbytes": ch.output_bytes}
+    declare = {"in": ch.input, "shared": ch.shared, "sel": ch.selector}
+    records = {"bytes": {}, "lebytes": {"little": True}, "sbytes": {"sign": True}, "lesbytes": {"little": True, "sign": True}}
+    emit_as = {"out": ch.output, "outbytes": ch.output_bytes, "outlebytes": lambda v: ch.output_bytes(v, little=True)}
+    signed = {"outsbytes": False, "outlesbytes": True}
     for st in [t.strip() for t in text.split(";") if t.strip()]:
         head, _, rest = st.partition(" ")
         if head in declare:
             for nm in [t.strip() for t in rest.split(",")]:
                 env[nm] = declare[head]()
-                if head == "bytes":                             # (the value and modimp's return value)
-                    env[nm], flags[nm] = env[nm]
+        elif head in records:
+            for nm in [t.strip() for t in rest.split(",")]:
+                got = ch.input_bytes(**records[head])           # (the value, modimp's return value and, where asked for, the sign)
+                env[nm], flags[nm] = got[:2]
+                signs.update({nm: got[2]} if len(got) == 3 else {})
         elif head in emit_as:
             for node in ast.parse("(%s,)" % rest, mode="eval").body.elts:
                 emit_as[head](ev(node))
+        elif head in signed:
+            for node in ast.parse("(%s,)" % rest, mode="eval").body.elts:
+                if not isinstance(node, ast.Tuple) or len(node.elts) != 2:
+                    raise ValueError("%s takes pairs (expression, int expression): %r" % (head, ast.unparse(node)))
+                ch.output_bytes(ev(node.elts[0]), little=signed[head], sign=ev(node.elts[1]))
         else:
             node = ast.parse(st).body[0]
             if not isinstance(node, ast.Assign) or len(node.targets) != 1:

@@ -29,6 +29,17 @@ lengths (13.5 % and 5.4 % ahead over all chains), and the tool EXITS 1 on the fi
 64 / 32 bits: modmul X25519 2.41 / 2.47, X448 2.19 / 2.39, NIST256 1.96 / 1.86, public-key check 1.36 / 1.25 -- over P-256 the kernels
 are bound by the Montgomery products of nres and redc, which fusing does not remove, and neither path reaches 2x there.
 
+With --le the tool measures the LITTLE-ENDIAN records instead (profiles/chain_le_rate.json, the table "chain_le_rate" of the document):
+`lebytes a, b; outlebytes modmul(a, b)` -- the body of (1), records least significant byte first: no bswap, the same traffic -- over
+X25519 and NIST256 at both word lengths and through both ways to the bytes, ALTERNATING in the same run with the big-endian chain of (1)
+on the same buffers and with the sequence a caller runs today (torch.flip x 2, modimp x 2, modmul, modexp, torch.flip).  Recorded per
+case: little-endian / big-endian per path beside the spread of the run's three readings (the kernel does strictly less work: the ratio
+is expected within that spread of 1), the big-endian figures against those the parent's profiles/chain_bytes_rate.json records (the
+shared frame did not move them), and call by call / shipped path, which the standing rule wants at 2 or more.  Then
+modarith_amd.fuse.rfc8032_decode_chain beside decompress_chain on the values the records spell: three exponentiations, no threshold,
+reported.  Exits 1 where a little-endian kernel is SLOWER than its big-endian twin by more than the spread, or the 2x rule fails.
+
+  python tools/chain_bytes_rate.py --le [--le-out profiles/chain_le_rate.json]     (GPU; --build-only and --table-from work with it)
   python tools/chain_bytes_rate.py [--log2n 24] [--launches 20] [--rounds 3] [--out profiles/chain_bytes_rate.json] [--doc docs/fused_chains.md]
   python tools/chain_bytes_rate.py --build-only                                   (hipcc only: the plug-ins the measurement loads)
   python tools/chain_bytes_rate.py --table-from profiles/chain_bytes_rate.json    (no GPU: rewrite the table of the document from a report)
@@ -47,6 +58,9 @@ REQUIRED = 2.0
 PRIMES = ("X25519", "NIST256", "X448")
 BMUL = "bytes a, b; outbytes modmul(a, b)"
 BEGIN, END = "<!-- chain_bytes_rate: table written by tools/chain_bytes_rate.py -->", "<!-- chain_bytes_rate: end -->"
+LE_PRIMES = ("X25519", "NIST256")
+LMUL = "lebytes a, b; outlebytes modmul(a, b)"
+LE_BEGIN, LE_END = "<!-- chain_le_rate: table written by tools/chain_bytes_rate.py --le -->", "<!-- chain_le_rate: end -->"
 
 
 def build_all(wls):
@@ -145,6 +159,149 @@ def pubkey(torch, F, f, extra, n, args, measure):
     return per
 
 
+# ---------------------------------------------------------------------------------------------------------------- little-endian records
+def build_le(wls):
+    from modarith_amd.fuse import decompress_chain, parse, rfc8032_decode_chain
+    out = {}
+    for wl in wls:
+        out[wl] = {"lmul/" + P: (parse(P, "rate_lmul", LMUL, wl=wl).build(), parse(P, "rate_bmul", BMUL, wl=wl).build()) for P in LE_PRIMES}
+        dec, (d,) = rfc8032_decode_chain("ED25519", wl, name="rate_rfc8032_decode")
+        dc, _ = decompress_chain("ED25519", wl, name="rate_decompress")
+        out[wl]["decode/X25519"] = (dec.build(), (dc.build(), d))
+    return out
+
+
+def lmul(torch, F, fle, fbe, n, args, measure, parent):
+    g = torch.Generator(device="cuda").manual_seed(101)
+    A, B = (torch.randint(0, 256, (n, F.nbytes), dtype=torch.uint8, device="cuda", generator=g) for _ in range(2))
+    out = torch.empty_like(A)
+
+    def calls():                                                 # what a caller of little-endian records runs today
+        x, _ = F.modimp(torch.flip(A, [1]))
+        y, _ = F.modimp(torch.flip(B, [1]))
+        F.modmul(x, y, out=x)
+        return torch.flip(F.modexp(x), [1])
+
+    want = calls()
+    bwant = F.modexp(F.modmul(F.modimp(A)[0], F.modimp(B)[0]))
+    for path in ("staged", "direct"):
+        for f, w, what in ((fle, want, "little"), (fbe, bwant, "big")):
+            out.zero_()
+            forced(path, lambda: f(A, B, out=[out]))()
+            assert torch.equal(out, w), "the fused %s-endian bytes on the %s path differ from the call sequence" % (what, path)
+    del want, bwant
+    torch.cuda.empty_cache()
+    fused = [("%s_%s" % (e, path), forced(path, lambda f=f: f(A, B, out=[out]))) for path in ("staged", "direct") for e, f in (("le", fle), ("be", fbe))]
+    readings = measure(torch, fused + [("calls", calls)], args.launches, args.rounds)
+    ms = {k: statistics.median(v) for k, v in readings.items()}
+    spread = max((max(readings[k]) - min(readings[k])) / min(readings[k]) for k, _ in fused)
+    per = {"readings_ms": readings, "ms": ms, "spread_of_fused_readings": spread, "nbytes": F.nbytes,
+           "bytes_per_element": {"fused": fle.chain.traffic_bytes(), "calls": fle.chain.unfused_traffic_bytes()},
+           "le_over_be": {path: ms["le_" + path] / ms["be_" + path] for path in ("staged", "direct")},
+           "be_recorded_by_parent_ms": {path: parent["ms"][path] for path in ("staged", "direct")} if parent else None,
+           "be_over_parent": {path: ms["be_" + path] / parent["ms"][path] for path in ("staged", "direct")} if parent else None}
+    per["le_within_spread_of_be"] = {path: abs(r - 1) <= spread for path, r in per["le_over_be"].items()}
+    per["be_within_spread_of_parent"] = {path: abs(r - 1) <= spread for path, r in per["be_over_parent"].items()} if parent else None
+    return per
+
+
+def decode(torch, F, f, extra, n, args, measure):
+    dc, d = extra
+    g = torch.Generator(device="cuda").manual_seed(107)
+    R = torch.randint(0, 256, (n, F.nbytes), dtype=torch.uint8, device="cuda", generator=g)
+    masked = torch.flip(R, [1]).contiguous()
+    masked[:, 0] &= 0x7f
+    s = (R[:, -1] >> 7).to(torch.int32)
+    y, fy = F.modimp(masked)
+    del masked
+    outs = [F.empty(n) for _ in range(3)] + [torch.empty(n, dtype=torch.int32, device="cuda")]
+    outs2 = [F.empty(n) for _ in range(3)] + [torch.empty(n, dtype=torch.int32, device="cuda")]
+    f(R, d, out=outs)
+    dc(y, d, s, out=outs2)
+    agree = fy == 1                                              # (where y was not below p the decode chain answers the neutral element)
+    assert torch.equal(outs[3][agree], outs2[3][agree]) and torch.equal(F.to_flat(outs[0])[:, agree], F.to_flat(outs2[0])[:, agree]), "decode differs from decompress"
+    readings = measure(torch, [("decode", lambda: f(R, d, out=outs)), ("decompress", lambda: dc(y, d, s, out=outs2))], args.launches, args.rounds)
+    ms = {k: statistics.median(v) for k, v in readings.items()}
+    return {"readings_ms": readings, "ms": ms, "decode_over_decompress": ms["decode"] / ms["decompress"], "points": int(outs[3].sum()),
+            "bytes_per_element": {"decode": f.chain.traffic_bytes(), "decompress": dc.chain.traffic_bytes()}}
+
+
+def le_table(report):
+    L = [LE_BEGIN, "",
+         "%s, %d elements, median of %d launches, %d readings (tools/chain_bytes_rate.py --le, profiles/chain_le_rate.json):" % (
+             report["device"], report["n"], report["launches"], report["rounds"]), "",
+         "| `outlebytes modmul(a, b)` | word length | LE staged ms | BE staged ms | LE / BE | LE direct ms | BE direct ms | LE / BE | spread of the run | BE now / parent's record (staged, direct) | call by call ms | call by call / shipped |",
+         "|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for k, c in report["cases"].items():
+        what, P, wl = k.split("/")
+        if what != "lmul":
+            continue
+        m = c["ms"]
+        par = "%.3f, %.3f" % (c["be_over_parent"]["staged"], c["be_over_parent"]["direct"]) if c["be_over_parent"] else ""
+        L.append("| %s (%d B) | %s | %.3f | %.3f | %.3f | %.3f | %.3f | %.3f | %.1f %% | %s | %.3f | %.2f |" % (
+            P, c["bytes_per_element"]["fused"], wl[1:], m["le_staged"], m["be_staged"], c["le_over_be"]["staged"], m["le_direct"], m["be_direct"], c["le_over_be"]["direct"],
+            100 * c["spread_of_fused_readings"], par, m["calls"], c["calls_over_shipped"]))
+    L += ["", "| `rfc8032_decode_chain` | word length | decode ms (records in) | `decompress_chain` ms (limbs and signs in) | decode / decompress |", "|---|---|---|---|---|"]
+    for k, c in report["cases"].items():
+        what, P, wl = k.split("/")
+        if what == "decode":
+            L.append("| ED25519 (%d B against %d B) | %s | %.3f | %.3f | %.3f |" % (c["bytes_per_element"]["decode"], c["bytes_per_element"]["decompress"], wl[1:],
+                                                                                 c["ms"]["decode"], c["ms"]["decompress"], c["decode_over_decompress"]))
+    return "\n".join(L + ["", LE_END])
+
+
+def main_le(args, wls):
+    built = build_le(wls)
+    if args.build_only:
+        return 0
+    import torch
+    assert torch.cuda.is_available(), "chain_bytes_rate.py measures on the GPU: no device, no number"
+    from chain_pred_rate import WARM_S, measure
+    from modarith_amd.field import Field
+    from modarith_amd.fuse import BYTES_IO_DEFAULT
+    os.environ.pop("MA_CHAIN_BYTES", None)
+    n = 1 << args.log2n
+    recorded = json.load(open(args.out))["cases"] if os.path.exists(args.out) else {}
+    report = {"n": n, "tile": args.tile, "launches": args.launches, "rounds": args.rounds, "warm_up_s": WARM_S, "device": torch.cuda.get_device_name(0),
+              "shipped": {"w%d" % wl: BYTES_IO_DEFAULT[wl] for wl in wls}, "parent_record": os.path.relpath(args.out, ROOT),
+              "timing": "device events around each launch, variants alternating on the same buffers; a reading is the median of the launches of one "
+                        "round, the figure the median of the readings", "cases": {}}
+    failed = []
+    for wl in wls:
+        for key, (f, extra) in built[wl].items():
+            what, P = key.split("/")
+            F = Field(P, wl=wl, tile=args.tile)
+            name = "%s/w%d" % (key, wl)
+            if what == "lmul":
+                per = lmul(torch, F, f, extra, n, args, measure, recorded.get("bmul/%s/w%d" % (P, wl)))
+                ship = BYTES_IO_DEFAULT[wl]
+                per["calls_over_shipped"], per["required"] = per["ms"]["calls"] / per["ms"]["le_" + ship], REQUIRED
+                print("%-18s LE staged %.3f direct %.3f | BE staged %.3f direct %.3f | LE / BE %.3f %.3f (spread %.1f %%) | call by call %.3f ms (x %.2f)" % (
+                    name, per["ms"]["le_staged"], per["ms"]["le_direct"], per["ms"]["be_staged"], per["ms"]["be_direct"], per["le_over_be"]["staged"],
+                    per["le_over_be"]["direct"], 100 * per["spread_of_fused_readings"], per["ms"]["calls"], per["calls_over_shipped"]), flush=True)
+                if per["calls_over_shipped"] < REQUIRED:
+                    failed.append("%s: the shipped path is %.2fx faster than call by call (required: %.1f)" % (name, per["calls_over_shipped"], REQUIRED))
+                for path, r in per["le_over_be"].items():
+                    if r - 1 > per["spread_of_fused_readings"]:
+                        failed.append("%s: little-endian %s is %.1f %% slower than big-endian (spread %.1f %%)" % (name, path, 100 * (r - 1), 100 * per["spread_of_fused_readings"]))
+            else:
+                per = decode(torch, F, f, extra, n, args, measure)
+                print("%-18s decode %.3f ms | decompress %.3f ms (x %.3f)" % (name, per["ms"]["decode"], per["ms"]["decompress"], per["decode_over_decompress"]), flush=True)
+            report["cases"][name] = per
+            del F
+            torch.cuda.empty_cache()
+    report["failed"] = failed
+    os.makedirs(os.path.dirname(os.path.abspath(args.le_out)), exist_ok=True)
+    with open(args.le_out, "w") as fh:
+        json.dump(report, fh, indent=1)
+    print("wrote", args.le_out)
+    if os.path.exists(args.doc):
+        write_table(args.doc, report, le_table, LE_BEGIN, LE_END)
+    for msg in failed:
+        print("FAILED:", msg)
+    return 1 if failed else 0
+
+
 def decide(report, shipped):
     """per word length: the totals of both paths over the chains measured, the run's spread, the path the rule picks and the one shipped"""
     out = {}
@@ -180,7 +337,7 @@ def table(report):
     return "\n".join(L + ["", END])
 
 
-def write_table(doc, report):
+def write_table(doc, report, table=table, BEGIN=BEGIN, END=END):
     text = open(doc).read()
     if BEGIN not in text or END not in text:
         raise SystemExit("%s has no table markers (%s ... %s)" % (doc, BEGIN, END))
@@ -200,11 +357,18 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "chain_bytes_rate.json"))
     ap.add_argument("--doc", default=os.path.join(ROOT, "docs", "fused_chains.md"))
     ap.add_argument("--table-from", default=None)
+    ap.add_argument("--le", action="store_true", help="measure the little-endian records (see the head of this file)")
+    ap.add_argument("--le-out", default=os.path.join(ROOT, "profiles", "chain_le_rate.json"))
     args = ap.parse_args()
     if args.table_from:
-        write_table(args.doc, json.load(open(args.table_from)))
+        if args.le:
+            write_table(args.doc, json.load(open(args.table_from)), le_table, LE_BEGIN, LE_END)
+        else:
+            write_table(args.doc, json.load(open(args.table_from)))
         return 0
     wls = [int(w) for w in args.wl.split(",")]
+    if args.le:
+        return main_le(args, wls)
     built = build_all(wls)
     if args.build_only:
         return 0
