@@ -11,12 +11,7 @@
 
 namespace ma {
 
-// COMB_ED25519_WINDOWS windows of COMB_ED25519_W bits x 2^(W-1) multiples x coordinates x limbs, the same for every lane: constant address space, wave-uniform indices
-__constant__ int32_t comb_ed25519[] = { COMB_ED25519_VALUES };
-struct CombED25519 {
-    static constexpr int W = COMB_ED25519_W, NW = COMB_ED25519_WINDOWS;
-    static __device__ __forceinline__ int32_t get(int idx) { return comb_ed25519[idx]; }
-};
+MA_COMB_TABLE(CombED25519, comb_ed25519, ED25519);       // csrc/comb.h
 
 // e*G through the fixed-base table, ONE scalar per lane.  SELF = false (the product path, round 5): the Edwards (X : Y : Z) go to the shared
 // inversion of csrc/edlad_k.h (one inversion per up to 32 records; rounds 2-4 shared one between the FOUR scalars of a lane).  SELF = true:

@@ -11,12 +11,7 @@
 
 namespace ma {
 
-// COMB_ED448_WINDOWS windows of COMB_ED448_W bits x 2^(W-1) multiples x coordinates x limbs, the same for every lane: constant address space, wave-uniform indices
-__constant__ int32_t comb_ed448[] = { COMB_ED448_VALUES };
-struct CombED448 {
-    static constexpr int W = COMB_ED448_W, NW = COMB_ED448_WINDOWS;
-    static __device__ __forceinline__ int32_t get(int idx) { return comb_ed448[idx]; }
-};
+MA_COMB_TABLE(CombED448, comb_ed448, ED448);       // csrc/comb.h
 
 // e*G through the fixed-base table, ONE scalar per lane.  SELF = false (the product path, round 5): the Edwards (X : Y : Z) go to the shared
 // inversion of csrc/edlad_k.h (one inversion per up to 32 records; rounds 2-4 shared one between the TWO scalars of a lane, the first

@@ -12,12 +12,7 @@
 
 namespace ma {
 
-// COMB_NIST256_WINDOWS windows of COMB_NIST256_W bits x 2^(W-1) multiples x coordinates x limbs, the same for every lane: constant address space, wave-uniform indices
-__constant__ int32_t comb_nist256[] = { COMB_NIST256_VALUES };
-struct CombNIST256 {
-    static constexpr int W = COMB_NIST256_W, NW = COMB_NIST256_WINDOWS;
-    static __device__ __forceinline__ int32_t get(int idx) { return comb_nist256[idx]; }
-};
+MA_COMB_TABLE(CombNIST256, comb_nist256, NIST256);       // csrc/comb.h
 
 // e*G, ONE scalar per lane, (X : Y : Z) to the inversion shared by up to 32 records (csrc/wn_export.h; round 5).  Rounds 2-4 shared one
 // inversion between the four scalars of a lane, whose four results cost 120 registers (the kernel below: 252-254 registers, two waves

@@ -12,12 +12,7 @@
 
 namespace ma {
 
-// COMB_SECP256K1_WINDOWS windows of COMB_SECP256K1_W bits x 2^(W-1) multiples x coordinates x limbs, the same for every lane: constant address space, wave-uniform indices
-__constant__ int32_t comb_secp256k1[] = { COMB_SECP256K1_VALUES };
-struct CombSECP256K1 {
-    static constexpr int W = COMB_SECP256K1_W, NW = COMB_SECP256K1_WINDOWS;
-    static __device__ __forceinline__ int32_t get(int idx) { return comb_secp256k1[idx]; }
-};
+MA_COMB_TABLE(CombSECP256K1, comb_secp256k1, SECP256K1);       // csrc/comb.h
 
 // e*G, ONE scalar per lane, (X : Y : Z) to the inversion shared by up to 32 records (csrc/wn_export.h; round 5).  Rounds 2-4 shared one
 // inversion between the four scalars of a lane, whose four results cost 120 registers (the kernel below: 252-254 registers, two waves

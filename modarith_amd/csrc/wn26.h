@@ -29,6 +29,7 @@
 #pragma once
 #include "fm26.h"
 #include "fk26.h"
+#include "comb.h"
 
 namespace ma {
 
@@ -416,22 +417,8 @@ struct Wn26 {
 // (bits BITS-W .. BITS-1 of s) is the top of w[4]
 template <int W, int BITS>
 MA_DEV void wn26_recode(const uint64_t* ew, uint64_t* w) {
-    constexpr auto cw = [](int k) {
-        uint64_t v = 0;
-        for (int b = 0; b < 64; b++) {
-            const int pos = 64 * k + b;
-            if (pos < BITS && pos % W == W - 1) v |= (uint64_t)1 << b;
-        }
-        return v;
-    };
-    unsigned __int128 acc = 0;
     uint64_t s[5];
-    static_for<0, 5>([&](auto K) {
-        constexpr int k = K;
-        acc += (unsigned __int128)(k < 4 ? ew[k < 4 ? k : 0] : 0) + cw(k);
-        s[k] = (uint64_t)acc;
-        acc >>= 64;
-    });
+    comb_bias_add<W, BITS, 4>(ew, s);
     constexpr int SH = 320 - BITS;           // 60 for 260 bits, 62 for 258
     static_for<0, 5>([&](auto KK) {
         constexpr int k = 4 - KK;
@@ -588,60 +575,19 @@ MA_DEV void wn26_mul2_get_one(const uint64_t* ew, const spint* PX, const spint* 
 
 // Fused GENERATOR multiplication + affine export: the affine coordinates of e*G -- ecnXXXgen, ecnXXXmul, ecnXXXget, the
 // opening of key generation and signing in the reference's ECDSA code (nist256.c:150-161 NIST256_KEY_PAIR, 214-222
-// NIST256_SIGN).  With the base point fixed the doublings disappear: e' = e + sum_i 2^(W-1) 2^(W i), digit_i = window_i(e')
-// - 2^(W-1), and e*G = sum_i digit_i * (2^(W i) G) with the NW x 2^(W-1) affine multiples precomputed (generated/comb_<C>.h:
-// W = 5, 52 windows x 16 entries, 66 560 bytes, the same table for every lane; W = 4 is 6 % slower, W = 6 -- 43 mixed
-// additions but 32 entries to scan -- no faster than W = 5 on P-256 and slower on secp256k1).  Per window ALL its entries are read through wave-uniform addresses (TAB: the
-// table in the constant address space, scalar loads) and selected by lane predication, the sign negates y, and one
-// complete MIXED addition follows; a zero digit adds (0, 0) and keeps the old sum.  52 mixed additions + a share of one
-// inversion per scalar against 256 doublings + 65 additions: the same bytes as ecn gen + ecn mul + ecn get for every scalar.
-// the walk over the windows of e: step(sx, sy, zero) is handed +-(the window's selected multiple of G), affine, or zero = true for a zero digit
+// NIST256_SIGN), through the fixed-base comb (csrc/comb.h; digits, bias, table and the measured window widths:
+// docs/curve_layer.md "The fixed-base comb").  Here: the entries of generated/comb_<C>.h are affine (x, y), the sign negates y, and one
+// complete MIXED addition follows per window; a zero digit hands on (0, 0) with zero = true and the step keeps the old sum.
+// step(sx, sy, zero) is handed +-(the window's selected multiple of G).
 template <class CV, class TAB, class STEP>
 MA_DEV void wn26_mulgen_walk(const uint64_t* ew, STEP step) {
     using F = typename CV::F;
-    constexpr int W = TAB::W, NW = TAB::NW, E2 = 1 << (W - 1);       // window width, windows, entries per window
-    static_assert(W * NW >= 257 && W * NW <= 316, "e + bias must fit the windows and five words");
-    uint64_t w[5];
-    {
-        uint64_t t[5];
-        wn26_recode<W, W * NW>(ew, t);              // left-aligned: undo, the windows are taken from the bottom here
-        constexpr int SH = 320 - W * NW;
-        static_for<0, 5>([&](auto K) {
-            constexpr int k = K;
-            w[k] = t[k] >> SH;
-            if constexpr (k < 4) w[k] |= t[k + 1] << (64 - SH);
-        });
-    }
-#pragma unroll 1
-    for (int i = 0; i < NW; i++) {
-        const int dgt = (int)((uint32_t)w[0] & (uint32_t)(2 * E2 - 1)) - E2;        // [-2^(W-1), 2^(W-1) - 1]
-        static_for<0, 5>([&](auto K) {
-            constexpr int k = K;
-            w[k] >>= W;
-            if constexpr (k < 4) w[k] |= w[k + 1] << (64 - W);
-        });
-        const bool neg = dgt < 0;
-        const uint32_t m = (uint32_t)(neg ? -dgt : dgt);        // 0 .. 2^(W-1)
-        // selection as OR of masked entries (exactly one mask is set, none for a zero digit): the entries sit in scalar
-        // registers, and v_and_or_b32 takes one of those next to two vector operands -- a v_cndmask would need a move first
-        // (its lane mask already uses the one scalar operand an instruction may read)
-        int32_t sx[10], sy[10], ny[10];
-        static_for<0, 10>([&](auto K) { sx[K] = 0; sy[K] = 0; });
-        static_for<0, E2>([&](auto MM) {
-            constexpr int mm = MM;
-            uint32_t mask = (m == (uint32_t)(mm + 1)) ? 0xffffffffu : 0u;
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm("" : "+v"(mask));       // opaque: otherwise the compiler turns (entry & mask) back into a select with a move
-#endif
-            static_for<0, 10>([&](auto K) {
-                sx[K] = (int32_t)((uint32_t)sx[K] | ((uint32_t)TAB::get(((i * E2 + mm) * 2 + 0) * 10 + K) & mask));
-                sy[K] = (int32_t)((uint32_t)sy[K] | ((uint32_t)TAB::get(((i * E2 + mm) * 2 + 1) * 10 + K) & mask));
-            });
-        });
-        F::neg(sy, ny);
-        F::select(neg, sy, ny, sy);
-        step(sx, sy, m == 0);
-    }
+    comb_walk<TAB, 4, 2, 10, 0u, int32_t>(ew, [&](int32_t (&sel)[2][10], bool neg, uint32_t m) {
+        int32_t ny[10];
+        F::neg(sel[1], ny);
+        F::select(neg, sel[1], ny, sel[1]);
+        step(sel[0], sel[1], m == 0);
+    });
 }
 template <class CV, class TAB, bool INIT = true>       // INIT = false: R += e*G (R holds a sum already)
 MA_DEV void wn26_mulgen_acc(const uint64_t* ew, typename Wn26<CV>::Pt& R) {

@@ -621,94 +621,73 @@ def w32_curve_unit_text(name: str, kind: str, field: str, nlimbs: int, montgomer
             % (up, kind, field, nlimbs, low, nlimbs, mul_wps or w32_curve_mul_wps(nlimbs, montgomery, kind), up, "edwards.h" if kind == "edwards" else "weierstrass.h", cls, low))
 
 
-COMB_CURVES = {"NIST256": (286, 5), "SECP256K1": (0, 5)}      # curve -> (log2 of the Montgomery factor of the fused kernels' field form, window width)
+# curve -> (window width, limb form of the fused kernels); the form decides the group law and how a table point is written
+COMB_CURVES = {"NIST256": (5, "fm26"), "SECP256K1": (5, "fk26"), "ED25519": (4, "fe26"), "ED448": (4, "fe28")}
+COMB_MONTGOMERY = {"fm26": 286, "fk26": 0}       # Weierstrass forms: log2 of the Montgomery factor of the fused kernels' field form
 
 
 def comb_header_text(name: str) -> str:
-    """fixed-base table of the fused generator multiplication (csrc/wn26.h wn26_mulgen_acc): for every W-bit window i
-    the affine multiples m * 2^(W i) * G, m = 1..2^(W-1), coordinates as ten 26-bit limbs of the fused kernels' field form
-    (value * 2^286 mod p for P-256, the plain value for secp256k1).  Plain integer curve arithmetic on the constants of
-    curves.py (curve.py:157-198)."""
-    from .curves import wcurve
-    c = wcurve(name)
-    p, a = c.fp.p, c.a
-    shift, W = COMB_CURVES[name]
-    windows = -(-(8 * c.fp.nbytes + 1) // W)
+    """fixed-base table of the fused generator multiplication (csrc/comb.h; docs/curve_layer.md "The fixed-base comb"): for every
+    W-bit window i the affine multiples m * 2^(W i) * G, m = 1..2^(W-1), one row each, as the mixed addition of the curve's
+    kernels reads them --
+    P-256 / secp256k1 (csrc/wn26.h): (x, y) as ten 26-bit limbs of the field form (value * 2^286 mod p for P-256, the plain value
+    for secp256k1); ED25519 (csrc/ed26.h): cached (y+x, y-x, 2dxy) as ten 25.5-bit limbs (fe26.h); ED448 (csrc/ed28.h): cached
+    (x, y, 39081 x y) as sixteen 28-bit limbs (fe28.h).
+    Plain integer curve arithmetic on the constants of curves.py (curve.py:85-105, 157-198)."""
+    from .curves import curve, wcurve
+    W, form = COMB_CURVES[name]
+    if form in COMB_MONTGOMERY:
+        c = wcurve(name)
+        p, a, neutral, shift = c.fp.p, c.a, None, COMB_MONTGOMERY[form]
 
-    def add(P, Q):
-        if P is None:
-            return Q
-        if Q is None:
-            return P
-        (x1, y1), (x2, y2) = P, Q
-        if x1 == x2:
-            if (y1 + y2) % p == 0:
-                return None
-            lam = (3 * x1 * x1 + a) * pow(2 * y1, -1, p) % p
-        else:
-            lam = (y2 - y1) * pow(x2 - x1, -1, p) % p
-        x3 = (lam * lam - x1 - x2) % p
-        return x3, (lam * (x1 - x3) - y1) % p
+        def add(P, Q):
+            if P is None:
+                return Q
+            if Q is None:
+                return P
+            (x1, y1), (x2, y2) = P, Q
+            if x1 == x2:
+                if (y1 + y2) % p == 0:
+                    return None
+                lam = (3 * x1 * x1 + a) * pow(2 * y1, -1, p) % p
+            else:
+                lam = (y2 - y1) * pow(x2 - x1, -1, p) % p
+            x3 = (lam * lam - x1 - x2) % p
+            return x3, (lam * (x1 - x3) - y1) % p
 
-    limbs = lambda v: [((v << shift) % p >> (26 * k)) & ((1 << 26) - 1) for k in range(10)]
-    rows = []
-    B = (c.gx, c.gy)
-    for i in range(windows):
-        T = None
-        for m in range(1, (1 << (W - 1)) + 1):
-            T = add(T, B)
-            rows.append("    " + ", ".join("0x%x" % v for v in limbs(T[0]) + limbs(T[1])) + ",   /* %d * 2^%d * G */ \\" % (m, W * i))
-        for _ in range(W):
-            B = add(B, B)
-    L = ["// GENERATED by modarith_amd/emit.py from modarith_amd/curves.py -- do not edit.",
-         "// Fixed-base table of %s for ecn_%s_mulgen_get_batch: [window 0..%d][multiple 1..%d][x, y][10 limbs of 26 bits]," % (
-             name, name.lower(), windows - 1, 1 << (W - 1)),
-         "// coordinates in the field form of the fused kernels (%s)." % ("value * 2^%d mod p" % shift if shift else "plain value"),
-         "#pragma once",
-         "#define COMB_%s_W %d" % (name, W),
-         "#define COMB_%s_WINDOWS %d" % (name, windows),
-         "#define COMB_%s_VALUES \\" % name] + rows + ["    /* end */", ""]
-    return "\n".join(L)
-
-
-COMB_EDWARDS = {"ED25519": (4, "fe26"), "ED448": (4, "fe28")}      # curve -> (window width, limb form)
-
-
-def comb_edwards_header_text(name: str) -> str:
-    """fixed-base table of the fused generator multiplication on the Edwards curves (csrc/ed26.h / ed28.h *_mulgen_get_one):
-    for every W-bit window i the affine multiples m * 2^(W i) * G, m = 1..2^(W-1), in the cached form of the mixed addition --
-    ED25519: (y+x, y-x, 2dxy) as ten 25.5-bit limbs (fe26.h), ED448: (x, y, 39081 x y) as sixteen 28-bit limbs (fe28.h).
-    Plain integer curve arithmetic on the constants of curves.py (curve.py:85-105)."""
-    from .curves import curve
-    c = curve(name)
-    p, a, d = c.fp.p, c.a, c.d % c.fp.p
-    W, form = COMB_EDWARDS[name]
-    windows = -(-(8 * c.fp.nbytes + 1) // W)
-
-    def add(P, Q):
-        (x1, y1), (x2, y2) = P, Q
-        t = d * x1 * x2 * y1 * y2 % p
-        return ((x1 * y2 + y1 * x2) * pow(1 + t, -1, p) % p, (y1 * y2 - a * x1 * x2) * pow(1 - t, -1, p) % p)
-
-    if form == "fe26":
-        pos = lambda i: (51 * i + 1) // 2
-        limbs = lambda v: [(v >> pos(i)) & ((1 << (25 if i & 1 else 26)) - 1) for i in range(10)]
-        cached = lambda x, y: limbs((y + x) % p) + limbs((y - x) % p) + limbs(2 * d * x * y % p)
+        limbs = lambda v: [((v << shift) % p >> (26 * k)) & ((1 << 26) - 1) for k in range(10)]
+        row = lambda x, y: limbs(x) + limbs(y)
+        layout = ["[x, y][10 limbs of 26 bits],", "// coordinates in the field form of the fused kernels (%s)." % ("value * 2^%d mod p" % shift if shift else "plain value")]
     else:
-        limbs = lambda v: [(v >> (28 * i)) & ((1 << 28) - 1) for i in range(16)]
-        cached = lambda x, y: limbs(x) + limbs(y) + limbs((-d) % p * x * y % p)
+        c = curve(name)
+        p, a, d, neutral = c.fp.p, c.a, c.d % c.fp.p, (0, 1)
+
+        def add(P, Q):
+            (x1, y1), (x2, y2) = P, Q
+            t = d * x1 * x2 * y1 * y2 % p
+            return ((x1 * y2 + y1 * x2) * pow(1 + t, -1, p) % p, (y1 * y2 - a * x1 * x2) * pow(1 - t, -1, p) % p)
+
+        if form == "fe26":
+            pos = lambda i: (51 * i + 1) // 2
+            limbs = lambda v: [(v >> pos(i)) & ((1 << (25 if i & 1 else 26)) - 1) for i in range(10)]
+            row = lambda x, y: limbs((y + x) % p) + limbs((y - x) % p) + limbs(2 * d * x * y % p)
+            layout = ["[y+x, y-x, 2dxy: 10 limbs of 25.5 bits][limbs]."]
+        else:
+            limbs = lambda v: [(v >> (28 * i)) & ((1 << 28) - 1) for i in range(16)]
+            row = lambda x, y: limbs(x) + limbs(y) + limbs((-d) % p * x * y % p)
+            layout = ["[x, y, 39081xy: 16 limbs of 28 bits][limbs]."]
+    windows = -(-(8 * c.fp.nbytes + 1) // W)
     rows = []
     B = (c.gx, c.gy)
     for i in range(windows):
-        T = (0, 1)
+        T = neutral
         for m in range(1, (1 << (W - 1)) + 1):
             T = add(T, B)
-            rows.append("    " + ", ".join("0x%x" % v for v in cached(*T)) + ",   /* %d * 2^%d * G */ \\" % (m, W * i))
+            rows.append("    " + ", ".join("0x%x" % v for v in row(*T)) + ",   /* %d * 2^%d * G */ \\" % (m, W * i))
         for _ in range(W):
             B = add(B, B)
     L = ["// GENERATED by modarith_amd/emit.py from modarith_amd/curves.py -- do not edit.",
-         "// Fixed-base table of %s for ecn_%s_mulgen_get_batch: [window 0..%d][multiple 1..%d][%s][limbs]." % (
-             name, name.lower(), windows - 1, 1 << (W - 1), "y+x, y-x, 2dxy: 10 limbs of 25.5 bits" if form == "fe26" else "x, y, 39081xy: 16 limbs of 28 bits"),
+         "// Fixed-base table of %s for ecn_%s_mulgen_get_batch: [window 0..%d][multiple 1..%d]%s" % (name, name.lower(), windows - 1, 1 << (W - 1), layout[0])] + layout[1:] + [
          "#pragma once",
          "#define COMB_%s_W %d" % (name, W),
          "#define COMB_%s_WINDOWS %d" % (name, windows),
@@ -850,8 +829,6 @@ def emit_all(primes=BUILT_PRIMES, out_dir: str = GEN_DIR) -> List[str]:
     paths = [_write(os.path.join(out_dir, "field_table.inc"), field_table_text(primes))]
     for name in COMB_CURVES:
         paths.append(_write(os.path.join(out_dir, "comb_%s.h" % name), comb_header_text(name)))
-    for name in COMB_EDWARDS:
-        paths.append(_write(os.path.join(out_dir, "comb_%s.h" % name), comb_edwards_header_text(name)))
     for name in EXTRA_PRIMES:
         if name in primes:
             paths.append(_write(os.path.join(out_dir, "capi_%s.hip" % name), capi_unit_text(name)))

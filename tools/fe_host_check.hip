@@ -4,6 +4,7 @@
 // the build container, without a GPU, before it goes to the box.  Usage: fe_host_check [n]  (exit code 0 = all equal)
 //   hipcc -O2 -std=c++17 tools/fe_host_check.hip -o /tmp/fe_host_check -Loracle -l:liboracle.so -Wl,-rpath,$PWD/oracle
 #define MA_DEV __host__ __device__ inline
+#define MA_COMB_SPACE static const       // csrc/comb.h: the fixed-base tables as plain host arrays
 #include "../modarith_amd/csrc/fe26.h"
 #include "../modarith_amd/csrc/fe28.h"
 #include "../modarith_amd/csrc/generated/curve_ED25519.h"
@@ -438,10 +439,8 @@ static int run_nist256_mul2(int n) {
 
 // fused generator multiplication on the Edwards curves (fixed-base tables generated/comb_<C>.h as host arrays) against the
 // oracle's ecn gen + ecn mul + ecn get: corner scalars (0, 1, single windows, 8 / 9 nibbles, all ones) and random ones
-static const int32_t comb_ed25519_host[] = { COMB_ED25519_VALUES };
-static const int32_t comb_ed448_host[] = { COMB_ED448_VALUES };
-struct HostComb25519 { static constexpr int W = COMB_ED25519_W, NW = COMB_ED25519_WINDOWS; static int32_t get(int idx) { return comb_ed25519_host[idx]; } };
-struct HostComb448 { static constexpr int W = COMB_ED448_W, NW = COMB_ED448_WINDOWS; static int32_t get(int idx) { return comb_ed448_host[idx]; } };
+MA_COMB_TABLE(HostComb25519, comb_ed25519_host, ED25519);
+MA_COMB_TABLE(HostComb448, comb_ed448_host, ED448);
 template <int NB, class PT, class FN, class GEN, class MUL, class GET>
 static int run_edgen(const char* name, int n, FN fused, GEN gen, MUL mul, GET get) {
     int bad = 0;

@@ -4,6 +4,7 @@
 // cannot do).  Test tooling, not product code.
 //   hipcc -O2 -std=c++17 -shared -fPIC --offload-host-only tools/wn26_host.hip -o /tmp/libwn26_host.so
 #define MA_DEV __host__ __device__ inline
+#define MA_COMB_SPACE static const       // csrc/comb.h: the fixed-base tables as plain host arrays
 #include "../modarith_amd/csrc/wn26.h"
 #include "../modarith_amd/csrc/generated/comb_NIST256.h"
 #include "../modarith_amd/csrc/generated/comb_SECP256K1.h"
@@ -36,10 +37,8 @@ extern "C" void wn26_field_product(int which, int mode, const int32_t* f, const 
 }
 
 // fused generator multiplication (wn26_mulgen_get_one) with the fixed-base tables as host arrays.  which = 0: P-256, 1: secp256k1
-static const int32_t comb_nist256_host[] = { COMB_NIST256_VALUES };
-static const int32_t comb_secp256k1_host[] = { COMB_SECP256K1_VALUES };
-struct HostCombNist256 { static constexpr int W = COMB_NIST256_W, NW = COMB_NIST256_WINDOWS; static int32_t get(int idx) { return comb_nist256_host[idx]; } };
-struct HostCombSecp256k1 { static constexpr int W = COMB_SECP256K1_W, NW = COMB_SECP256K1_WINDOWS; static int32_t get(int idx) { return comb_secp256k1_host[idx]; } };
+MA_COMB_TABLE(HostCombNist256, comb_nist256_host, NIST256);
+MA_COMB_TABLE(HostCombSecp256k1, comb_secp256k1_host, SECP256K1);
 extern "C" void wn26_mulgen_get_host(int which, const uint64_t* ew, uint64_t* xw, uint64_t* yw) {
     if (which == 0) ma::wn26_mulgen_get_one<ma::CvNist256, HostCombNist256>(ew, xw, yw);
     else ma::wn26_mulgen_get_one<ma::CvSecp256k1, HostCombSecp256k1>(ew, xw, yw);
