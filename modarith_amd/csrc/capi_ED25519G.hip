@@ -107,16 +107,10 @@ extern "C" size_t ecn_ed25519_mulgen2_get_workspace_bytes(size_t n) { return ed2
 extern "C" int ecn_ed25519_mulgen2_get_batch(const char* e, const char* f, const ma_spint* Q, char* x, char* y, int* sign, size_t n, size_t ld,
                                              void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mulgen2_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, f, x, y)) return reject("ecn mulgen2_get: byte records must be 8-byte aligned");
     hipStream_t s = (hipStream_t)st;
     EdLadScratch ws(workspace, workspace_bytes, ed26l_workspace_bytes(n), 8, s);
-    if (!ws.p) {
-        set_error(std::string("ecn mulgen2_get: no usable workspace -- " + std::string(ws.why) + " (pass ecn_ed25519_mulgen2_get_workspace_bytes(n) bytes; the library's own scratch pool is not available while the stream is being captured)"));
-        return (int)hipErrorInvalidValue;
-    }
+    if (!ws.p) return reject("ecn mulgen2_get: no usable workspace -- " + std::string(ws.why) + " (pass ecn_ed25519_mulgen2_get_workspace_bytes(n) bytes; the library's own scratch pool is not available while the stream is being captured)");
     const unsigned char *eb = reinterpret_cast<const unsigned char*>(e), *fb = reinterpret_cast<const unsigned char*>(f);
     edlad_pipeline<LadT25519, 2>(Q, ld, reinterpret_cast<unsigned char*>(x), reinterpret_cast<unsigned char*>(y), sign, n, ws.p, s,
                                  [&](size_t first, size_t m, const Ed26lWs& w) { k_ed25519_lad_gen2<<<(unsigned)((m + 63) / 64), 64, 0, s>>>(eb, fb, first, w); });
@@ -125,10 +119,7 @@ extern "C" int ecn_ed25519_mulgen2_get_batch(const char* e, const char* f, const
 
 extern "C" int ecn_ed25519_mulgen_get_batch(const char* e, char* x, char* y, int* sign, size_t n, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mulgen_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, x, y)) return reject("ecn mulgen_get: byte records must be 8-byte aligned");
     hipStream_t s = (hipStream_t)st;
     const unsigned char* eb = reinterpret_cast<const unsigned char*>(e);
     unsigned char *xb = reinterpret_cast<unsigned char*>(x), *yb = reinterpret_cast<unsigned char*>(y);
@@ -149,10 +140,7 @@ extern "C" int ecn_ed25519_mulgen_get_batch(const char* e, char* x, char* y, int
 // bv = [bk](9): rfc7748(bk, base, bv) of rfc7748.c:297-333 for a batch of private keys, on the fixed-base table
 extern "C" int rfc7748_X25519_base_batch(const char* bk, char* bv, size_t n, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(bk) | reinterpret_cast<uintptr_t>(bv)) & 7u) {
-        set_error("rfc7748 base: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(bk, bv)) return reject("rfc7748 base: byte records must be 8-byte aligned");
     const size_t lanes = ((n + MULGEN_G - 1) / MULGEN_G + 63) / 64 * 64, cap = (size_t)4 * 1024 * 64;
     k_x25519_base<<<(unsigned)((lanes < cap ? lanes : cap) / 64), 64, 0, (hipStream_t)st>>>(
         reinterpret_cast<const uint64_t*>(bk), reinterpret_cast<uint64_t*>(bv), n);

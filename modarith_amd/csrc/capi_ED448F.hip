@@ -43,16 +43,10 @@ extern "C" size_t ecn_ed448_mul_get_workspace_bytes(size_t n) { return ed28l_wor
 extern "C" int ecn_ed448_mul_get_batch(const char* e, const ma_spint* P, char* x, char* y, int* sign, size_t n, size_t ld,
                                        void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mul_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, x, y)) return reject("ecn mul_get: byte records must be 8-byte aligned");
     hipStream_t s = (hipStream_t)st;
     EdLadScratch ws(workspace, workspace_bytes, ed28l_workspace_bytes(n), 8, s);
-    if (!ws.p) {
-        set_error(std::string("ecn mul_get: no usable workspace -- " + std::string(ws.why) + " (pass ecn_ed448_mul_get_workspace_bytes(n) bytes; the library's own scratch pool is not available while the stream is being captured)"));
-        return (int)hipErrorInvalidValue;
-    }
+    if (!ws.p) return reject("ecn mul_get: no usable workspace -- " + std::string(ws.why) + " (pass ecn_ed448_mul_get_workspace_bytes(n) bytes; the library's own scratch pool is not available while the stream is being captured)");
     const unsigned char* eb = reinterpret_cast<const unsigned char*>(e);
     edlad_pipeline<LadT448, 1>(P, ld, reinterpret_cast<unsigned char*>(x), reinterpret_cast<unsigned char*>(y), sign, n, ws.p, s,
                                [&](size_t first, size_t m, const Ed28lWs& w) { k_ed448_lad<<<(unsigned)((m + 63) / 64), 64, 0, s>>>(eb, first, w); });

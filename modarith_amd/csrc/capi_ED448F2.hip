@@ -41,11 +41,7 @@ void k_ed448_mul2_straus(const unsigned char* e, const spint* Pb, const unsigned
         for (int which = 0; which < 2; which++) {
             const spint* B = which ? Qb : Pb;
             spint X[8], Y[8], Z[8];
-            static_for<0, 8>([&](auto I) {
-                X[I] = B[(size_t)I * ld + first + t()];
-                Y[I] = B[(size_t)(8 + I) * ld + first + t()];
-                Z[I] = B[(size_t)(16 + I) * ld + first + t()];
-            });
+            load_xyz<8>(B, ld, first, t, X, Y, Z);
             S::build(tab, which, X, Y, Z);
         }
         W448_4Lds de{ce}, df{cf};
@@ -74,16 +70,10 @@ extern "C" size_t ecn_ed448_mul2_get_workspace_bytes(size_t n) { return mul2_get
 extern "C" int ecn_ed448_mul2_get_batch(const char* e, const ma_spint* P, const char* f, const ma_spint* Q, char* x, char* y, int* sign,
                                         size_t n, size_t ld, void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mul2_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, f, x, y)) return reject("ecn mul2_get: byte records must be 8-byte aligned");
     hipStream_t s = (hipStream_t)st;
     EdLadScratch wsp(workspace, workspace_bytes, mul2_get_net_bytes(n), 128, s);
-    if (!wsp.p) {
-        set_error(std::string("ecn mul2_get: no usable workspace -- " + std::string(wsp.why) + " (pass ecn_ed448_mul2_get_workspace_bytes(n) bytes; the library's own scratch pool is not available while the stream is being captured)"));
-        return (int)hipErrorInvalidValue;
-    }
+    if (!wsp.p) return reject("ecn mul2_get: no usable workspace -- " + std::string(wsp.why) + " (pass ecn_ed448_mul2_get_workspace_bytes(n) bytes; the library's own scratch pool is not available while the stream is being captured)");
     const unsigned char *eb = reinterpret_cast<const unsigned char*>(e), *fb = reinterpret_cast<const unsigned char*>(f);
     const size_t slab_bytes = straus_waves(n < EDLAD_CHUNK ? n : EDLAD_CHUNK) * STRAUS448_SLAB_BYTES_PER_WAVE;
     for (size_t first = 0; first < n; first += EDLAD_CHUNK) {

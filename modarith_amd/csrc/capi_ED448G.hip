@@ -134,16 +134,10 @@ extern "C" size_t ecn_ed448_mulgen2_get_workspace_bytes(size_t n) { return ed28l
 extern "C" int ecn_ed448_mulgen2_get_batch(const char* e, const char* f, const ma_spint* Q, char* x, char* y, int* sign, size_t n, size_t ld,
                                            void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mulgen2_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, f, x, y)) return reject("ecn mulgen2_get: byte records must be 8-byte aligned");
     hipStream_t s = (hipStream_t)st;
     EdLadScratch ws(workspace, workspace_bytes, ed28l_workspace_bytes(n), 8, s);
-    if (!ws.p) {
-        set_error(std::string("ecn mulgen2_get: no usable workspace -- " + std::string(ws.why) + " (pass ecn_ed448_mulgen2_get_workspace_bytes(n) bytes; the library's own scratch pool is not available while the stream is being captured)"));
-        return (int)hipErrorInvalidValue;
-    }
+    if (!ws.p) return reject("ecn mulgen2_get: no usable workspace -- " + std::string(ws.why) + " (pass ecn_ed448_mulgen2_get_workspace_bytes(n) bytes; the library's own scratch pool is not available while the stream is being captured)");
     const unsigned char *eb = reinterpret_cast<const unsigned char*>(e), *fb = reinterpret_cast<const unsigned char*>(f);
     edlad_pipeline<LadT448, 2>(Q, ld, reinterpret_cast<unsigned char*>(x), reinterpret_cast<unsigned char*>(y), sign, n, ws.p, s,
                                [&](size_t first, size_t m, const Ed28lWs& w) { k_ed448_lad_gen2<<<(unsigned)((m + 63) / 64), 64, 0, s>>>(eb, fb, first, w); });
@@ -152,10 +146,7 @@ extern "C" int ecn_ed448_mulgen2_get_batch(const char* e, const char* f, const m
 
 extern "C" int ecn_ed448_mulgen_get_batch(const char* e, char* x, char* y, int* sign, size_t n, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mulgen_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, x, y)) return reject("ecn mulgen_get: byte records must be 8-byte aligned");
     hipStream_t s = (hipStream_t)st;
     const unsigned char* eb = reinterpret_cast<const unsigned char*>(e);
     unsigned char *xb = reinterpret_cast<unsigned char*>(x), *yb = reinterpret_cast<unsigned char*>(y);
@@ -176,10 +167,7 @@ extern "C" int ecn_ed448_mulgen_get_batch(const char* e, char* x, char* y, int* 
 // bv = [bk](5): rfc7748(bk, base, bv) for a batch of private keys, on the fixed-base table of ED448 (4-isogenous to curve448)
 extern "C" int rfc7748_X448_base_batch(const char* bk, char* bv, size_t n, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(bk) | reinterpret_cast<uintptr_t>(bv)) & 7u) {
-        set_error("rfc7748 base: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(bk, bv)) return reject("rfc7748 base: byte records must be 8-byte aligned");
     hipStream_t s = (hipStream_t)st;
     const uint64_t* kb = reinterpret_cast<const uint64_t*>(bk);
     uint64_t* vb = reinterpret_cast<uint64_t*>(bv);
@@ -189,9 +177,7 @@ extern "C" int rfc7748_X448_base_batch(const char* bk, char* bv, size_t n, void*
         if (ws.p) {
             Ed28lWs w(ws.p, m);
             k_x448_base<false><<<(unsigned)((m + 63) / 64), 64, 0, s>>>(kb, vb, first, m, w);
-            size_t L;
-            int rounds;
-            edlad_rounds(m, &L, &rounds);
+            const auto [L, rounds] = shared_inv_rounds(m);
             k_fe_batch_div<Fe28, 16, 7, SinkLE448, 4><<<(unsigned)((L + 63) / 64), 64, 0, s>>>(w.A, w.B, w.B, w.wc, m, L, rounds, SinkLE448{vb, first});
         } else {
             k_x448_base<true><<<(unsigned)((m + 63) / 64), 64, 0, s>>>(kb, vb, first, m, Ed28lWs(nullptr, m));

@@ -17,20 +17,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_nist256_table(const spint* Pb, size_t ld, WnAffWs ws) {
     const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= ws.m) return;
-    Wj26::table_of([&](spint* X, spint* Y, spint* Z) {
-        static_for<0, 5>([&](auto I) {
-            X[I] = Pb[(size_t)I * ld + t];
-            Y[I] = Pb[(size_t)(5 + I) * ld + t];
-            Z[I] = Pb[(size_t)(10 + I) * ld + t];
-        });
-    }, ws, t);
+    Wj26::table_of([&](spint* X, spint* Y, spint* Z) { load_xyz<5>(Pb, ld, 0, t, X, Y, Z); }, ws, t);
 }
 // the window loop on the affine table: one record per lane, the recoded scalar in LDS (one byte per window), (X : Y : Z) of the result to
 // the shared inversion
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void k_nist256_mul_get(const unsigned char* e, WnAffWs ws, WnExpWs ex) {
     using P = P_NIST256;
-    using DIG = WnLds<4, 260>;
+    using DIG = WjLds;
     __shared__ unsigned char digs[DIG::ROWS * 64];
     const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= ws.m) return;
@@ -56,14 +50,9 @@ extern "C" size_t ecn_nist256_mul_get_workspace_bytes(size_t n) { return WnAffWs
 extern "C" int ecn_nist256_mul_get_batch(const char* e, const ma_spint* P, char* x, char* y, int* sign, size_t n, size_t ld,
                                          void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mul_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
-    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) || workspace_bytes < ecn_nist256_mul_get_workspace_bytes(n)) {
-        set_error("ecn mul_get: workspace missing, not 8-byte aligned or too small (see ecn_nist256_mul_get_workspace_bytes)");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, x, y)) return reject("ecn mul_get: byte records must be 8-byte aligned");
+    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) || workspace_bytes < ecn_nist256_mul_get_workspace_bytes(n))
+        return reject("ecn mul_get: workspace missing, not 8-byte aligned or too small (see ecn_nist256_mul_get_workspace_bytes)");
     hipStream_t s = (hipStream_t)st;
     const unsigned char* eb = reinterpret_cast<const unsigned char*>(e);
     char* wsb = reinterpret_cast<char*>(workspace);

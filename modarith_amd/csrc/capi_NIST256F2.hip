@@ -20,13 +20,7 @@ void k_nist256_tables(const spint* Pb, const spint* Qb, size_t ld, WnAffWs ws) {
     const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= ws.m) return;
     auto point = [&](const spint* B) {
-        return [&, B](spint* X, spint* Y, spint* Z) {
-            static_for<0, 5>([&](auto I) {
-                X[I] = B[(size_t)I * ld + t];
-                Y[I] = B[(size_t)(5 + I) * ld + t];
-                Z[I] = B[(size_t)(10 + I) * ld + t];
-            });
-        };
+        return [&, B](spint* X, spint* Y, spint* Z) { load_xyz<5>(B, ld, 0, t, X, Y, Z); };
     };
     Wj26::table_of(point(Pb), ws, t, 0);
     Wj26::table_of(point(Qb), ws, t, 8);
@@ -34,7 +28,7 @@ void k_nist256_tables(const spint* Pb, const spint* Qb, size_t ld, WnAffWs ws) {
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_nist256_mul2_get(const unsigned char* e, const unsigned char* f, WnAffWs ws, WnExpWs ex) {
     using P = P_NIST256;
-    using DIG = WnLds<4, 260>;
+    using DIG = WjLds;
     __shared__ unsigned char digs[2 * DIG::ROWS * 64];
     const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= ws.m) return;
@@ -62,14 +56,9 @@ extern "C" size_t ecn_nist256_mul2_get_workspace_bytes(size_t n) { return WnAffW
 extern "C" int ecn_nist256_mul2_get_batch(const char* e, const ma_spint* P, const char* f, const ma_spint* Q, char* x, char* y, int* sign,
                                           size_t n, size_t ld, void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mul2_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
-    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) || workspace_bytes < ecn_nist256_mul2_get_workspace_bytes(n)) {
-        set_error("ecn mul2_get: workspace missing, not 8-byte aligned or too small (see ecn_nist256_mul2_get_workspace_bytes)");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, f, x, y)) return reject("ecn mul2_get: byte records must be 8-byte aligned");
+    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) || workspace_bytes < ecn_nist256_mul2_get_workspace_bytes(n))
+        return reject("ecn mul2_get: workspace missing, not 8-byte aligned or too small (see ecn_nist256_mul2_get_workspace_bytes)");
     hipStream_t s = (hipStream_t)st;
     char* wsb = reinterpret_cast<char*>(workspace);
     for (size_t first = 0; first < n; first += WNAFF_CHUNK) {

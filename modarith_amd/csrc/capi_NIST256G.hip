@@ -43,11 +43,7 @@ void k_nist256_mulgen_get(const unsigned char* e, unsigned char* xb, unsigned ch
             [&](int g, spint* ew) { const size_t tg = t + (size_t)g * lanes; load_be_record<P>(e, tg < n ? tg : t, ew); }, xw, yw);
         static_for<0, MULGEN_G>([&](auto GI) {
             const size_t tg = t + (size_t)GI * lanes;
-            if (tg < n) {
-                if (xb) store_be_record<P>(xb, tg, xw[GI]);
-                if (yb) store_be_record<P>(yb, tg, yw[GI]);
-                if (sign) sign[tg] = !yb ? (int)(yw[GI][0] & 1) : (!xb ? (int)(xw[GI][0] & 1) : 0);
-            }
+            if (tg < n) store_affine_be<P>(xb, yb, sign, tg, xw[GI], yw[GI]);
         });
     }
 }
@@ -58,18 +54,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_nist256_table2(const spint* Qb, size_t ld, WnAffWs ws) {
     const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= ws.m) return;
-    Wj26::table_of([&](spint* X, spint* Y, spint* Z) {
-        static_for<0, 5>([&](auto I) {
-            X[I] = Qb[(size_t)I * ld + t];
-            Y[I] = Qb[(size_t)(5 + I) * ld + t];
-            Z[I] = Qb[(size_t)(10 + I) * ld + t];
-        });
-    }, ws, t);
+    Wj26::table_of([&](spint* X, spint* Y, spint* Z) { load_xyz<5>(Qb, ld, 0, t, X, Y, Z); }, ws, t);
 }
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void k_nist256_mulgen2_get(const unsigned char* e, const unsigned char* f, WnAffWs ws, WnExpWs ex) {
     using P = P_NIST256;
-    using DIG = WnLds<4, 260>;
+    using DIG = WjLds;
     __shared__ unsigned char digs[DIG::ROWS * 64];          // f's windows in LDS
     const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= ws.m) return;
@@ -98,14 +88,9 @@ extern "C" size_t ecn_nist256_mulgen2_get_workspace_bytes(size_t n) { return WnA
 extern "C" int ecn_nist256_mulgen2_get_batch(const char* e, const char* f, const ma_spint* Q, char* x, char* y, int* sign, size_t n, size_t ld,
                                            void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mulgen2_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
-    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) || workspace_bytes < ecn_nist256_mulgen2_get_workspace_bytes(n)) {
-        set_error("ecn mulgen2_get: workspace missing, not 8-byte aligned or too small (see ecn_nist256_mulgen2_get_workspace_bytes)");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, f, x, y)) return reject("ecn mulgen2_get: byte records must be 8-byte aligned");
+    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) || workspace_bytes < ecn_nist256_mulgen2_get_workspace_bytes(n))
+        return reject("ecn mulgen2_get: workspace missing, not 8-byte aligned or too small (see ecn_nist256_mulgen2_get_workspace_bytes)");
     hipStream_t s = (hipStream_t)st;
     char* wsb = reinterpret_cast<char*>(workspace);
     for (size_t first = 0; first < n; first += WNAFF_CHUNK) {
@@ -124,10 +109,7 @@ extern "C" int ecn_nist256_mulgen2_get_batch(const char* e, const char* f, const
 
 extern "C" int ecn_nist256_mulgen_get_batch(const char* e, char* x, char* y, int* sign, size_t n, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mulgen_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, x, y)) return reject("ecn mulgen_get: byte records must be 8-byte aligned");
     hipStream_t s = (hipStream_t)st;
     EdLadScratch ws(nullptr, 0, WnExpWs::bytes(n), 8, s);              // no workspace argument: the library's scratch pool
     if (ws.p) {

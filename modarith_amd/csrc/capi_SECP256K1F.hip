@@ -34,11 +34,7 @@ void k_secp256k1_mul_get(const unsigned char* e, const spint* Pb, size_t ld, uin
             dig.fill(ew, col);
         }
         spint X[5], Y[5], Z[5];
-        static_for<0, 5>([&](auto I) {
-            X[I] = Pb[(size_t)I * ld + t()];
-            Y[I] = Pb[(size_t)(5 + I) * ld + t()];
-            Z[I] = Pb[(size_t)(10 + I) * ld + t()];
-        });
+        load_xyz<5>(Pb, ld, 0, t, X, Y, Z);
         Wn26<CvSecp256k1>::Pt R;
         secp256k1_glv_mul_acc(dig, X, Y, Z, T, R);
         ex.store<Fk26>(t(), R.X, R.Y, R.Z);
@@ -63,14 +59,9 @@ extern "C" size_t ecn_secp256k1_mul_get_workspace_bytes(size_t n) { return slab_
 extern "C" int ecn_secp256k1_mul_get_batch(const char* e, const ma_spint* P, char* x, char* y, int* sign, size_t n, size_t ld,
                                          void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mul_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
-    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) || workspace_bytes < ecn_secp256k1_mul_get_workspace_bytes(n)) {
-        set_error("ecn mul_get: workspace missing, not 8-byte aligned or too small (see ecn_secp256k1_mul_get_workspace_bytes)");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, x, y)) return reject("ecn mul_get: byte records must be 8-byte aligned");
+    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) || workspace_bytes < ecn_secp256k1_mul_get_workspace_bytes(n))
+        return reject("ecn mul_get: workspace missing, not 8-byte aligned or too small (see ecn_secp256k1_mul_get_workspace_bytes)");
     hipStream_t s = (hipStream_t)st;
     for (size_t first = 0; first < n; first += WNEXP_CHUNK) {
         const size_t m = n - first < WNEXP_CHUNK ? n - first : WNEXP_CHUNK;

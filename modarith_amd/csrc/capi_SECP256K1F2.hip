@@ -37,13 +37,7 @@ void k_secp256k1_mul2_get(const unsigned char* e, const spint* Pb, const unsigne
             df.fill(ew, cf);
         }
         auto point = [&](const spint* B) {                   // the 3 x 5 limbs of record t() of a point batch, fetched when its table is built
-            return [&, B](spint* X, spint* Y, spint* Z) {
-                static_for<0, 5>([&](auto I) {
-                    X[I] = B[(size_t)I * ld + t()];
-                    Y[I] = B[(size_t)(5 + I) * ld + t()];
-                    Z[I] = B[(size_t)(10 + I) * ld + t()];
-                });
-            };
+            return [&, B](spint* X, spint* Y, spint* Z) { load_xyz<5>(B, ld, 0, t, X, Y, Z); };
         };
         Wn26<CvSecp256k1>::Pt R;
         secp256k1_glv_mul2_acc_ld(de, point(Pb), df, point(Qb), T, R);
@@ -68,14 +62,9 @@ extern "C" size_t ecn_secp256k1_mul2_get_workspace_bytes(size_t n) { return slab
 extern "C" int ecn_secp256k1_mul2_get_batch(const char* e, const ma_spint* P, const char* f, const ma_spint* Q, char* x, char* y, int* sign,
                                           size_t n, size_t ld, void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mul2_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
-    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) || workspace_bytes < ecn_secp256k1_mul2_get_workspace_bytes(n)) {
-        set_error("ecn mul2_get: workspace missing, not 8-byte aligned or too small (see ecn_secp256k1_mul2_get_workspace_bytes)");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, f, x, y)) return reject("ecn mul2_get: byte records must be 8-byte aligned");
+    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) || workspace_bytes < ecn_secp256k1_mul2_get_workspace_bytes(n))
+        return reject("ecn mul2_get: workspace missing, not 8-byte aligned or too small (see ecn_secp256k1_mul2_get_workspace_bytes)");
     hipStream_t s = (hipStream_t)st;
     for (size_t first = 0; first < n; first += WNEXP_CHUNK) {
         const size_t m = n - first < WNEXP_CHUNK ? n - first : WNEXP_CHUNK;

@@ -42,11 +42,7 @@ void k_secp256k1_mulgen_get(const unsigned char* e, unsigned char* xb, unsigned 
             [&](int g, spint* ew) { const size_t tg = t + (size_t)g * lanes; load_be_record<P>(e, tg < n ? tg : t, ew); }, xw, yw);
         static_for<0, MULGEN_G>([&](auto GI) {
             const size_t tg = t + (size_t)GI * lanes;
-            if (tg < n) {
-                if (xb) store_be_record<P>(xb, tg, xw[GI]);
-                if (yb) store_be_record<P>(yb, tg, yw[GI]);
-                if (sign) sign[tg] = !yb ? (int)(yw[GI][0] & 1) : (!xb ? (int)(xw[GI][0] & 1) : 0);
-            }
+            if (tg < n) store_affine_be<P>(xb, yb, sign, tg, xw[GI], yw[GI]);
         });
     }
 }
@@ -71,11 +67,7 @@ void k_secp256k1_mulgen2_get(const unsigned char* e, const unsigned char* f, con
             dig.fill(fw, col);
         }
         spint X[5], Y[5], Z[5];
-        static_for<0, 5>([&](auto I) {
-            X[I] = Qb[(size_t)I * ld + t()];
-            Y[I] = Qb[(size_t)(5 + I) * ld + t()];
-            Z[I] = Qb[(size_t)(10 + I) * ld + t()];
-        });
+        load_xyz<5>(Qb, ld, 0, t, X, Y, Z);
         Wn26<CvSecp256k1>::Pt R;
         secp256k1_glv_mul_acc(dig, X, Y, Z, T, R);
         spint ew[4];
@@ -102,14 +94,9 @@ extern "C" size_t ecn_secp256k1_mulgen2_get_workspace_bytes(size_t n) { return s
 extern "C" int ecn_secp256k1_mulgen2_get_batch(const char* e, const char* f, const ma_spint* Q, char* x, char* y, int* sign, size_t n, size_t ld,
                                            void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mulgen2_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
-    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) || workspace_bytes < ecn_secp256k1_mulgen2_get_workspace_bytes(n)) {
-        set_error("ecn mulgen2_get: workspace missing, not 8-byte aligned or too small (see ecn_secp256k1_mulgen2_get_workspace_bytes)");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, f, x, y)) return reject("ecn mulgen2_get: byte records must be 8-byte aligned");
+    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) || workspace_bytes < ecn_secp256k1_mulgen2_get_workspace_bytes(n))
+        return reject("ecn mulgen2_get: workspace missing, not 8-byte aligned or too small (see ecn_secp256k1_mulgen2_get_workspace_bytes)");
     hipStream_t s = (hipStream_t)st;
     for (size_t first = 0; first < n; first += WNEXP_CHUNK) {
         const size_t m = n - first < WNEXP_CHUNK ? n - first : WNEXP_CHUNK;
@@ -122,10 +109,7 @@ extern "C" int ecn_secp256k1_mulgen2_get_batch(const char* e, const char* f, con
 
 extern "C" int ecn_secp256k1_mulgen_get_batch(const char* e, char* x, char* y, int* sign, size_t n, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7u) {
-        set_error("ecn mulgen_get: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(e, x, y)) return reject("ecn mulgen_get: byte records must be 8-byte aligned");
     hipStream_t s = (hipStream_t)st;
     EdLadScratch ws(nullptr, 0, WnExpWs::bytes(n), 8, s);              // no workspace argument: the library's scratch pool
     if (ws.p) {

@@ -36,6 +36,25 @@ inline unsigned grid_for(size_t nthreads, int block = 256, bool tiled = false) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// the host preamble of the fused entry points: is any of the byte-record arrays off an 8-byte boundary (a null pointer -- an output
+// the caller does not want -- counts as aligned), and the refusal of a call: the text to modarith_amd_last_error(), hipErrorInvalidValue back
+template <class... PTR>
+inline bool records_misaligned(const PTR*... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 7u) != 0; }
+inline int reject(const std::string& msg) {
+    set_error(msg);
+    return (int)hipErrorInvalidValue;
+}
+
+// the lanes and rounds of an inversion shared down a column of records (Montgomery's trick; csrc/edlad_k.h, wn_export.h, wn_affine.h,
+// capi_prime.inc): one round per 65 536 records, at most cap, at least 1; lane j of L takes records j, j + L, ..., j + (rounds - 1) L
+struct SharedInvRounds { size_t L; int rounds; };
+inline SharedInvRounds shared_inv_rounds(size_t m, size_t cap = 32) {
+    size_t r = (m + 65535) / 65536;
+    if (r > cap) r = cap;
+    if (r < 1) r = 1;
+    return {(m + r - 1) / r, (int)r};
+}
+
 // Failures of the host side that the reference's void / predicate signatures cannot return (the scalar _ct entry points: no staging
 // buffer, a failed copy, a failed launch): recorded, never fatal.  fail() sets the calling thread's modarith_amd_last_error() text and
 // the process-wide sticky status modarith_amd_status() (first error code since the last modarith_amd_clear_status()); the entry point

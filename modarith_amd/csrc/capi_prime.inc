@@ -168,14 +168,9 @@ constexpr size_t LADDER_SPLIT_MIN = 8192;
 size_t LADDER_WS(MA_NAME)(size_t n) { return n * (LADDER_NW * sizeof(uint64_t) + LADDER_NL * sizeof(uint32_t)); }
 int LADDER_BATCH_WS(MA_NAME)(const char* bk, const char* bu, char* bv, size_t n, void* workspace, size_t workspace_bytes, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(bk) | reinterpret_cast<uintptr_t>(bu) | reinterpret_cast<uintptr_t>(bv) | reinterpret_cast<uintptr_t>(workspace)) & 7u) {
-        set_error("rfc7748: byte records and workspace must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
-    if (workspace == nullptr || workspace_bytes < LADDER_WS(MA_NAME)(n)) {
-        set_error("rfc7748 batch_ws: workspace too small (see rfc7748_<CURVE>_batch_workspace_bytes)");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(bk, bu, bv, workspace)) return reject("rfc7748: byte records and workspace must be 8-byte aligned");
+    if (workspace == nullptr || workspace_bytes < LADDER_WS(MA_NAME)(n))
+        return reject("rfc7748 batch_ws: workspace too small (see rfc7748_<CURVE>_batch_workspace_bytes)");
     hipStream_t s = (hipStream_t)st;
     const int block = ladder_block();
     if (ladder_use_field()) {
@@ -189,10 +184,8 @@ int LADDER_BATCH_WS(MA_NAME)(const char* bk, const char* bu, char* bv, size_t n,
     uint32_t* wc = reinterpret_cast<uint32_t*>(wz + (size_t)LADDER_NW * n);
     LADDER_XZ_KERNEL<<<grid_for(n, block), block, 0, s>>>(reinterpret_cast<const uint64_t*>(bk), reinterpret_cast<const uint64_t*>(bu),
                                                          reinterpret_cast<uint64_t*>(bv), wz, n);
-    size_t rounds = (n + 65535) / 65536;
-    if (rounds > 32) rounds = 32;
-    const size_t L = (n + rounds - 1) / rounds;
-    k_fe_finish<LadderFe, LADDER_NL, LADDER_NW><<<(unsigned)((L + 63) / 64), 64, 0, s>>>(reinterpret_cast<uint64_t*>(bv), wz, wc, n, L, (int)rounds);
+    const auto [L, rounds] = shared_inv_rounds(n);
+    k_fe_finish<LadderFe, LADDER_NL, LADDER_NW><<<(unsigned)((L + 63) / 64), 64, 0, s>>>(reinterpret_cast<uint64_t*>(bv), wz, wc, n, L, rounds);
     return check_launch("rfc7748(split)");
 }
 // the split form on a stream-ordered workspace of the library's own, when that is possible: not while the stream is being
@@ -213,10 +206,7 @@ static bool ladder_try_split(const char* bk, const char* bu, char* bv, size_t n,
 #endif
 int LADDER_BATCH(MA_NAME)(const char* bk, const char* bu, char* bv, size_t n, void* st) {
     if (n == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(bk) | reinterpret_cast<uintptr_t>(bu) | reinterpret_cast<uintptr_t>(bv)) & 7u) {
-        set_error("rfc7748: byte records must be 8-byte aligned");
-        return (int)hipErrorInvalidValue;
-    }
+    if (records_misaligned(bk, bu, bv)) return reject("rfc7748: byte records must be 8-byte aligned");
     const int block = ladder_block();
 #if defined(MA_LADDER_FE26) || defined(MA_LADDER_FE28)
     // the fused 32-bit-limb ladders (csrc/fe26.h: X25519 on 10 x 25.5 bits; csrc/fe28.h: X448 on 16 x 28 bits);

@@ -7,9 +7,9 @@
 
 namespace ma {
 
-// s = e + bias, NS + 1 words from the bottom; bias: a 1 in every bit position b < BITS with b % W == W - 1, folded per word at
-// compile time.  Window i of s minus 2^(W-1) is then the signed digit i of e, with no carries between digits.
-template <int W, int BITS, int NS>
+// s = e + bias, NO words from the bottom (e: NS words); bias: a 1 in every bit position b < BITS with b % W == W - 1, folded per
+// word at compile time.  Window i of s minus 2^(W-1) is then the signed digit i of e, with no carries between digits.
+template <int W, int BITS, int NS, int NO = NS + 1>
 MA_DEV void comb_bias_add(const uint64_t* ew, uint64_t* s) {
     constexpr auto cw = [](int k) {
         uint64_t v = 0;
@@ -20,7 +20,7 @@ MA_DEV void comb_bias_add(const uint64_t* ew, uint64_t* s) {
         return v;
     };
     unsigned __int128 acc = 0;
-    static_for<0, NS + 1>([&](auto K) {
+    static_for<0, NO>([&](auto K) {
         constexpr int k = K;
         acc += (unsigned __int128)(k < NS ? ew[k < NS ? k : 0] : 0) + cw(k);
         s[k] = (uint64_t)acc;

@@ -54,18 +54,6 @@ struct CurveOps {
     static constexpr int NB = P::NBYTES;
     static constexpr int NW = (NB + 7) / 8;          // 64-bit words of a scalar / coordinate record
     static constexpr int PADB = 8 * NW - NB;         // unused top bytes of the top word (6 for the 66-byte NIST521 records)
-    // v <<= S over W words, S a compile-time bit count
-    template <int S, int W>
-    static MA_DEV void shl_words(word_t* v) {
-        constexpr int ws = S / 64, bs = S % 64;
-        static_for<0, W>([&](auto KK) {
-            constexpr int k = W - 1 - KK;
-            word_t x = 0;
-            if constexpr (k - ws >= 0) x = v[k - ws] << bs;
-            if constexpr (bs != 0 && k - ws - 1 >= 0) x |= v[k - ws - 1] >> (64 - bs);
-            v[k] = x;
-        });
-    }
     struct Point { limb_t x[NL], y[NL], z[NL]; };
 
     static MA_DEV void cpy(const Point& q, Point& p) { F::modcpy(q.x, p.x); F::modcpy(q.y, p.y); F::modcpy(q.z, p.z); }

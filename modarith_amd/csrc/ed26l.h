@@ -99,11 +99,7 @@ struct Ed26Lad {
         // the step of fe26.h x25519_fe26_ladder (selects instead of swaps: the pair {DA, CB} does not see the swap), 256 bits, no clamp
 #pragma unroll 1
         for (int step = 0; step < 256; step++) {
-            const uint32_t kt = (uint32_t)(kw[3] >> 63);
-            kw[3] = (kw[3] << 1) | (kw[2] >> 63);
-            kw[2] = (kw[2] << 1) | (kw[1] >> 63);
-            kw[1] = (kw[1] << 1) | (kw[0] >> 63);
-            kw[0] <<= 1;
+            const uint32_t kt = take_top_bit<4>(kw);
             const bool sw = (swap ^ kt) != 0;
             swap = kt;
             uint32_t A[10], B[10], Cc[10], D[10], As[10], Bs[10], AA[10], BB[10], Ee[10];

@@ -16,6 +16,7 @@
 // 256 x (4S + 3M) + 65 M (T before an addition) + 65 x (8M + 7M) + 2 x 7 x 8M (tables) = 2.5e5 multiply-adds per pair.
 #pragma once
 #include "ed26.h"
+#include "window.h"
 
 namespace ma {
 
@@ -139,45 +140,9 @@ struct Ed26Straus {
     }
 };
 
-// e' = e + sum_{i<65} 8*16^i (260 bits), window 64 first
-struct W25519_4Regs {
-    uint64_t w[5];
-    MA_DEV void init(const uint64_t* in) {
-        unsigned __int128 acc = 0;
-        uint64_t s[5];
-        static_for<0, 5>([&](auto K) {
-            constexpr int k = K;
-            acc += (unsigned __int128)(k < 4 ? in[k < 4 ? k : 0] : 0) + (k < 4 ? 0x8888888888888888ull : 0x8ull);
-            s[k] = (uint64_t)acc;
-            acc >>= 64;
-        });
-        // left-align: bit 259 -> bit 63 of w[4]
-        w[4] = (s[4] << 60) | (s[3] >> 4);
-        w[3] = (s[3] << 60) | (s[2] >> 4);
-        w[2] = (s[2] << 60) | (s[1] >> 4);
-        w[1] = (s[1] << 60) | (s[0] >> 4);
-        w[0] = s[0] << 60;
-    }
-    MA_DEV uint32_t window(int) {
-        const uint32_t win = (uint32_t)(w[4] >> 60);
-        w[4] = (w[4] << 4) | (w[3] >> 60);
-        w[3] = (w[3] << 4) | (w[2] >> 60);
-        w[2] = (w[2] << 4) | (w[1] >> 60);
-        w[1] = (w[1] << 4) | (w[0] >> 60);
-        w[0] <<= 4;
-        return win;
-    }
-};
-struct W25519_4Lds {                        // one byte per window in the lane's column of an LDS array
-    const unsigned char* col;
-    static MA_DEV void fill(const uint64_t* in, unsigned char* col) {
-        W25519_4Regs r;
-        r.init(in);
-#pragma unroll 1
-        for (int i = 0; i < 65; i++) col[(size_t)i * 64] = (unsigned char)r.window(i);
-    }
-    MA_DEV uint32_t window(int i) const { return col[(size_t)i * 64]; }
-};
+// e' = e + sum_{i<65} 8*16^i (260 bits), window 64 first (csrc/window.h); Lds: one byte per window in the lane's column of an LDS array
+using W25519_4Regs = WinRegs<4, 260, 4>;
+using W25519_4Lds = WinLds<4, 260, 4>;
 
 // the tables as a plain array (host check) ...
 struct StrausTabArray {

@@ -70,12 +70,7 @@ struct Ed28Lad {
         uint32_t swap = 0;
 #pragma unroll 1
         for (int step = 0; step < 448; step++) {
-            const uint32_t kt = (uint32_t)(kw[6] >> 63);
-            static_for<0, 7>([&](auto KK) {
-                constexpr int k = 6 - KK;
-                kw[k] <<= 1;
-                if constexpr (k > 0) kw[k] |= kw[k - 1] >> 63;
-            });
+            const uint32_t kt = take_top_bit<7>(kw);
             const bool sw = (swap ^ kt) != 0;
             swap = kt;
             uint32_t A[16], B[16], C[16], D[16], As[16], Bs[16], AA[16], BB[16], Ee[16], t[16];

@@ -12,6 +12,7 @@
 // goes through the shared inversion of csrc/edlad_k.h.
 #pragma once
 #include "ed28.h"
+#include "window.h"
 
 namespace ma {
 
@@ -113,43 +114,9 @@ struct Ed28Straus {
     }
 };
 
-// e' = e + sum_{i<113} 8*16^i (452 bits), window 112 first
-struct W448_4Regs {
-    uint64_t w[8];
-    MA_DEV void init(const uint64_t* in) {
-        unsigned __int128 acc = 0;
-        uint64_t s[8];
-        static_for<0, 8>([&](auto K) {
-            constexpr int k = K;
-            acc += (unsigned __int128)(k < 7 ? in[k < 7 ? k : 0] : 0) + (k < 7 ? 0x8888888888888888ull : 0x8ull);
-            s[k] = (uint64_t)acc;
-            acc >>= 64;
-        });
-        // left-align: bit 451 -> bit 63 of w[7]
-        static_for<0, 8>([&](auto KK) {
-            constexpr int k = 7 - KK;
-            w[k] = (s[k] << 60) | (k > 0 ? s[k > 0 ? k - 1 : 0] >> 4 : 0);
-        });
-    }
-    MA_DEV uint32_t window(int) {
-        const uint32_t win = (uint32_t)(w[7] >> 60);
-        static_for<0, 8>([&](auto KK) {
-            constexpr int k = 7 - KK;
-            w[k] = (w[k] << 4) | (k > 0 ? w[k > 0 ? k - 1 : 0] >> 60 : 0);
-        });
-        return win;
-    }
-};
-struct W448_4Lds {                          // one byte per window in the lane's column of an LDS array
-    const unsigned char* col;
-    static MA_DEV void fill(const uint64_t* in, unsigned char* col) {
-        W448_4Regs r;
-        r.init(in);
-#pragma unroll 1
-        for (int i = 0; i < 113; i++) col[(size_t)i * 64] = (unsigned char)r.window(i);
-    }
-    MA_DEV uint32_t window(int i) const { return col[(size_t)i * 64]; }
-};
+// e' = e + sum_{i<113} 8*16^i (452 bits), window 112 first (csrc/window.h); Lds: one byte per window in the lane's column of an LDS array
+using W448_4Regs = WinRegs<4, 452, 7>;
+using W448_4Lds = WinLds<4, 452, 7>;
 
 // the tables as a plain array (host check) ...
 struct Straus448TabArray {

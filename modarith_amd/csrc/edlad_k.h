@@ -75,11 +75,7 @@ __global__ __launch_bounds__(256) void k_edlad_prep(const spint* Pb, size_t firs
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= ws.m) return;
     spint X[T::NIN], Y[T::NIN], Z[T::NIN];
-    static_for<0, T::NIN>([&](auto I) {
-        X[I] = Pb[(size_t)I * ld + first + t];
-        Y[I] = Pb[(size_t)(T::NIN + I) * ld + first + t];
-        Z[I] = Pb[(size_t)(2 * T::NIN + I) * ld + first + t];
-    });
+    load_xyz<T::NIN>(Pb, ld, first, t, X, Y, Z);
     uint32_t D[T::NL], nu[T::NL], nw[T::NL];
     const uint32_t fl = T::prep(X, Y, Z, D, nu, nw);
     uint64_t w[T::NW];
@@ -99,27 +95,14 @@ struct SinkExportBE {
     int* sign;
     size_t first;
     MA_DEV void operator()(size_t e, uint64_t* xw, uint64_t* yw) const {
-        const size_t t = first + e;
-        if (xb) store_be_record<P>(xb, t, xw);
-        if (yb) store_be_record<P>(yb, t, yw);
-        if (sign) sign[t] = !yb ? (int)(yw[0] & 1) : (!xb ? (int)(xw[0] & 1) : 0);
+        store_affine_be<P>(xb, yb, sign, first + e, xw, yw);
     }
 };
-
-inline void edlad_rounds(size_t m, size_t* L, int* rounds) {
-    size_t r = (m + 65535) / 65536;
-    if (r > 32) r = 32;
-    if (r < 1) r = 1;
-    *rounds = (int)r;
-    *L = (m + r - 1) / r;
-}
 
 // the second shared inversion + export of a chunk
 template <class T, int TAG>
 void edlad_export(const EdLadWs<T>& ws, unsigned char* x, unsigned char* y, int* sign, size_t first, hipStream_t s) {
-    size_t L;
-    int rounds;
-    edlad_rounds(ws.m, &L, &rounds);
+    const auto [L, rounds] = shared_inv_rounds(ws.m);
     k_fe_batch_div<typename T::F, T::NL, T::NW, SinkExportBE<typename T::P>, TAG><<<(unsigned)((L + 63) / 64), 64, 0, s>>>(
         ws.A, ws.B, ws.Cn, ws.wc, ws.m, L, rounds, SinkExportBE<typename T::P>{x, y, sign, first});
 }
@@ -129,9 +112,7 @@ int edlad_pipeline(const spint* P, size_t ld, unsigned char* x, unsigned char* y
     for (size_t first = 0; first < n; first += EDLAD_CHUNK) {
         const size_t m = n - first < EDLAD_CHUNK ? n - first : EDLAD_CHUNK;
         EdLadWs<T> ws(workspace, m);
-        size_t L;
-        int rounds;
-        edlad_rounds(m, &L, &rounds);
+        const auto [L, rounds] = shared_inv_rounds(m);
         k_edlad_prep<T, TAG><<<(unsigned)((m + 255) / 256), 256, 0, s>>>(P, first, ld, ws);
         k_fe_batch_div<typename T::F, T::NL, T::NW, SinkWords<T::NW>, TAG><<<(unsigned)((L + 63) / 64), 64, 0, s>>>(
             ws.A, ws.B, ws.Cn, ws.wc, m, L, rounds, SinkWords<T::NW>{ws.B, ws.Cn, m});

@@ -257,11 +257,7 @@ MA_DEV void x25519_fe26_ladder(const uint64_t* kw_in, const uint64_t* uw_in, uin
     uw[3] &= 0x7fffffffffffffffull;                     // mask bit 255 of u (rfc7748.c:171-172)
     kw[0] &= ~7ull;                                     // clamp (rfc7748.c:135-141)
     kw[3] = (kw[3] & 0x7fffffffffffffffull) | 0x4000000000000000ull;
-    // left-align: bit 254 -> bit 63 of kw[3]
-    kw[3] = (kw[3] << 1) | (kw[2] >> 63);
-    kw[2] = (kw[2] << 1) | (kw[1] >> 63);
-    kw[1] = (kw[1] << 1) | (kw[0] >> 63);
-    kw[0] <<= 1;
+    shl_words<1, 4>(kw);                                // left-align: bit 254 -> bit 63 of kw[3]
 
     uint32_t x1[10], x1_19[10], x3[10], z3[10];
     F::from_words(uw, x1);
@@ -275,11 +271,7 @@ MA_DEV void x25519_fe26_ladder(const uint64_t* kw_in, const uint64_t* uw_in, uin
     uint32_t swap = 0;
 #pragma unroll 1
     for (int step = 0; step < 255; step++) {
-        const uint32_t kt = (uint32_t)(kw[3] >> 63);
-        kw[3] = (kw[3] << 1) | (kw[2] >> 63);
-        kw[2] = (kw[2] << 1) | (kw[1] >> 63);
-        kw[1] = (kw[1] << 1) | (kw[0] >> 63);
-        kw[0] <<= 1;
+        const uint32_t kt = take_top_bit<4>(kw);
         const bool sw = (swap ^ kt) != 0;
         swap = kt;
         uint32_t A[10], B[10], C[10], D[10], As[10], Bs[10], AA[10], BB[10], E[10];

@@ -85,6 +85,29 @@ MA_DEV void static_for(Fn&& fn) {
     }
 }
 
+// v <<= S over W words, S a compile-time bit count
+template <int S, int W>
+MA_DEV void shl_words(word_t* v) {
+    constexpr int ws = S / 64, bs = S % 64;
+    static_for<0, W>([&](auto KK) {
+        constexpr int k = W - 1 - KK;
+        word_t x = 0;
+        if constexpr (k - ws >= 0) x = v[k - ws] << bs;
+        if constexpr (bs != 0 && k - ws - 1 >= 0) x |= v[k - ws - 1] >> (64 - bs);
+        v[k] = x;
+    });
+}
+// the top B bits of the NW words of v, then v <<= B: one step of a scalar walked from the top (B = 1: the ladders; the windows of
+// csrc/window.h)
+template <int B, int NW>
+MA_DEV uint32_t take_top_bits(word_t* v) {
+    const uint32_t top = (uint32_t)(v[NW - 1] >> (64 - B));
+    shl_words<B, NW>(v);
+    return top;
+}
+template <int NW>
+MA_DEV uint32_t take_top_bit(word_t* v) { return take_top_bits<1, NW>(v); }
+
 // 64x64 -> 128 product.  gfx950 has no 64-bit multiplier; the compiler lowers this to four
 // v_mad_u64_u32 plus carries.
 MA_DEV dpint mulw(spint a, spint b) { return (dpint)a * (dpint)b; }

@@ -115,28 +115,10 @@ struct GlvSecp256k1 {
 };
 
 // signed 4-bit digits of a magnitude below 2^131 (three words): s = k + sum_{i<33} 8 * 16^i, digit_i = window_i(s) - 8, windows
-// taken from the top (wn26_recode for 132 bits in three words)
-struct Glv4Regs {
-    uint64_t w[3];
-    MA_DEV void init(const uint64_t* k) {
-        constexpr uint64_t B = 0x8888888888888888ull;
-        const unsigned __int128 a0 = (unsigned __int128)k[0] + B;
-        const unsigned __int128 a1 = (unsigned __int128)k[1] + B + (uint64_t)(a0 >> 64);
-        const uint64_t s2 = k[2] + 0x8u + (uint64_t)(a1 >> 64);
-        const uint64_t s0 = (uint64_t)a0, s1 = (uint64_t)a1;
-        w[2] = (s2 << 60) | (s1 >> 4);
-        w[1] = (s1 << 60) | (s0 >> 4);
-        w[0] = s0 << 60;
-    }
-    MA_DEV uint32_t take() {
-        const uint32_t win = (uint32_t)(w[2] >> 60);
-        w[2] = (w[2] << 4) | (w[1] >> 60);
-        w[1] = (w[1] << 4) | (w[0] >> 60);
-        w[0] <<= 4;
-        return win;
-    }
-};
-constexpr int GLV_WINDOWS = 33;
+// taken from the top (csrc/window.h: 132 bits in three words)
+using Glv4Regs = WinRegs<4, 132, 3>;
+using Glv4Lds = WinLds<4, 132, 3>;
+constexpr int GLV_WINDOWS = Glv4Lds::COUNT;                     // 33
 
 // digit sources for the two half scalars: window(which, i) for i = 0, 1, ... in order, neg(which) = the half scalar's sign
 struct GlvRegs {
@@ -148,24 +130,19 @@ struct GlvRegs {
         r[0].init(k1);
         r[1].init(k2);
     }
-    MA_DEV uint32_t window(int which, int) { return which ? r[1].take() : r[0].take(); }
+    MA_DEV uint32_t window(int which, int i) { return which ? r[1].window(i) : r[0].window(i); }
     MA_DEV bool neg(int which) const { return which ? n[1] : n[0]; }
 };
 struct GlvLds {
     static constexpr int COUNT = 2 * GLV_WINDOWS;               // bytes per lane column
     const unsigned char* col;
     bool n[2];
-    // one byte per window in the lane's column of an LDS array (as wn26.h WnLds), written before the point is loaded
+    // one byte per window in the lane's column of an LDS array, the first half's windows then the second's, written before the point is loaded
     MA_DEV void fill(const uint64_t* ew, unsigned char* c) {
         uint64_t k1[3], k2[3];
         GlvSecp256k1::split(ew, k1, n[0], k2, n[1]);
-        Glv4Regs r;
-        r.init(k1);
-#pragma unroll 1
-        for (int i = 0; i < GLV_WINDOWS; i++) c[(size_t)i * 64] = (unsigned char)r.take();
-        r.init(k2);
-#pragma unroll 1
-        for (int i = 0; i < GLV_WINDOWS; i++) c[(size_t)(GLV_WINDOWS + i) * 64] = (unsigned char)r.take();
+        Glv4Lds::fill(k1, c);
+        Glv4Lds::fill(k2, c + (size_t)GLV_WINDOWS * 64);
         col = c;
     }
     MA_DEV uint32_t window(int which, int i) const { return col[(size_t)(which * GLV_WINDOWS + i) * 64]; }

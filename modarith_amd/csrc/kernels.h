@@ -639,6 +639,29 @@ __device__ __forceinline__ void store_be_record(unsigned char* bytes, size_t t, 
         });
     }
 }
+// What a fused call hands back of the affine point (xw, yw) of record t (ecnXXXget): the x record if asked for, the y record if asked
+// for, and the sign: the parity of the coordinate that is NOT written (of y first), 0 when both are
+template <class P>
+__device__ __forceinline__ void store_affine_be(unsigned char* xb, unsigned char* yb, int* sign, size_t t, const word_t* xw, const word_t* yw) {
+    if (xb) store_be_record<P>(xb, t, xw);
+    if (yb) store_be_record<P>(yb, t, yw);
+    if (sign) sign[t] = !yb ? (int)(yw[0] & 1) : (!xb ? (int)(xw[0] & 1) : 0);
+}
+// The three coordinates of record first + t of a batch of projective points: limb rows ld apart, X's N rows, then Y's, then Z's.  t: the
+// index, or a callable that yields it and is called afresh for every limb -- the kernels that keep a 64-bit index out of their loops that
+// way (one index held across the fifteen loads spilled two more scalar registers in k_ed448_mul2_straus)
+template <int N, class T>
+__device__ __forceinline__ void load_xyz(const spint* B, size_t ld, size_t first, T t, spint* X, spint* Y, spint* Z) {
+    auto at = [&]() -> size_t {
+        if constexpr (std::is_invocable_v<T>) return t();
+        else return t;
+    };
+    static_for<0, N>([&](auto I) {
+        X[I] = B[(size_t)I * ld + first + at()];
+        Y[I] = B[(size_t)(N + I) * ld + first + at()];
+        Z[I] = B[(size_t)(2 * N + I) * ld + first + at()];
+    });
+}
 // The same records least significant byte first (the RFC 7748 / RFC 8032 wire formats; what the reference's reverse() makes of them
 // before modimp): word k of the integer is chunk k as it lies in memory, no swap and no reversal of the word order; bytes are
 // assembled one by one where NBYTES is no multiple of 8, at word length 32 through the opaque form of load_be_record -- the same

@@ -41,22 +41,11 @@ __global__ __launch_bounds__(256) void k_rfc7748(const spint* bk, const spint* b
         // step reads that bit and shifts the multi-word scalar left by one (static register indices
         // only, one copy of the step body in the instruction stream)
         constexpr int LSH = 64 * NW - NBITS;
-        if constexpr (LSH > 0) {
-            static_for<0, NW>([&](auto KK) {
-                constexpr int k = NW - 1 - KK;
-                kw[k] <<= LSH;
-                if constexpr (k > 0) kw[k] |= kw[k - 1] >> (64 - LSH);
-            });
-        }
+        shl_words<LSH, NW>(kw);
         int swap = 0;
 #pragma unroll 1
         for (int step = 0; step < NBITS; step++) {
-            const int kt = (int)(kw[NW - 1] >> 63);
-            static_for<0, NW>([&](auto KK) {
-                constexpr int k = NW - 1 - KK;
-                kw[k] <<= 1;
-                if constexpr (k > 0) kw[k] |= kw[k - 1] >> 63;
-            });
+            const int kt = (int)take_top_bit<NW>(kw);
             swap ^= kt;
             F::modcsw(swap, x2, x3);
             F::modcsw(swap, z2, z3);

@@ -33,6 +33,10 @@
 
 namespace ma {
 
+// the digit sources of the window loops below: 65 signed 4-bit windows and one per-lane flag kept beside them (csrc/window.h)
+using WjRegs = WinRegsPark<WinRegs<4, 260, 4>>;
+using WjLds = WinLdsPark<WinLds<4, 260, 4>>;
+
 struct Wj26 {
     using F = Fm26;
     using E = Wn26<CvNist256>;

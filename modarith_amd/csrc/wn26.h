@@ -29,7 +29,7 @@
 #pragma once
 #include "fm26.h"
 #include "fk26.h"
-#include "comb.h"
+#include "window.h"
 
 namespace ma {
 
@@ -413,57 +413,10 @@ struct Wn26 {
     }
 };
 
-// s = e + bias (bias: a 1 in bit positions b < BITS with b % W == W - 1), then left-aligned so that the top window
-// (bits BITS-W .. BITS-1 of s) is the top of w[4]
-template <int W, int BITS>
-MA_DEV void wn26_recode(const uint64_t* ew, uint64_t* w) {
-    uint64_t s[5];
-    comb_bias_add<W, BITS, 4>(ew, s);
-    constexpr int SH = 320 - BITS;           // 60 for 260 bits, 62 for 258
-    static_for<0, 5>([&](auto KK) {
-        constexpr int k = 4 - KK;
-        w[k] = s[k] << SH;
-        if constexpr (k > 0) w[k] |= s[k - 1] >> (64 - SH);
-    });
-}
-template <int W>
-MA_DEV uint32_t wn26_take(uint64_t* w) {
-    const uint32_t win = (uint32_t)(w[4] >> (64 - W));
-    static_for<0, 5>([&](auto KK) {
-        constexpr int k = 4 - KK;
-        w[k] <<= W;
-        if constexpr (k > 0) w[k] |= w[k - 1] >> (64 - W);
-    });
-    return win;
-}
-
-// ---- digit sources and table accessors (round 4; the concepts of ed28.h): Regs = the shift registers above, Lds = one byte per
-// window in the lane's column of an LDS array, written before the point is loaded; the table accessor is ed28.h's TabStrided
-// (host check, round-3 layout) or TabSlab (per-wave slab, row addresses formed at the access).  window(i) for i = 0, 1, ... in order.
-template <int W, int BITS>
-struct WnRegs {
-    uint64_t w[5];
-    uint32_t flag = 0;
-    MA_DEV void init(const uint64_t* ew) { wn26_recode<W, BITS>(ew, w); }
-    MA_DEV uint32_t window(int) { return wn26_take<W>(w); }
-    MA_DEV void park(uint32_t v) { flag = v; }                  // one per-lane flag kept beside the digits (WnLds: in LDS, not in a register)
-    MA_DEV uint32_t parked() const { return flag; }
-};
-template <int W, int BITS>
-struct WnLds {
-    static constexpr int COUNT = (BITS + W - 1) / W;            // 65 windows of 4 bits (260), 86 of 3 bits (258)
-    static constexpr int ROWS = COUNT + 1;                      // + one row for a per-lane flag (park / parked)
-    unsigned char* col;
-    static MA_DEV void fill(const uint64_t* ew, unsigned char* col) {
-        WnRegs<W, BITS> r;
-        r.init(ew);
-#pragma unroll 1
-        for (int i = 0; i < COUNT; i++) col[(size_t)i * 64] = (unsigned char)r.window(i);
-    }
-    MA_DEV uint32_t window(int i) const { return col[(size_t)i * 64]; }
-    MA_DEV void park(uint32_t v) { col[(size_t)COUNT * 64] = (unsigned char)v; }
-    MA_DEV uint32_t parked() const { return col[(size_t)COUNT * 64]; }
-};
+// ---- digit sources and table accessors (round 4; the concepts of ed28.h): the digit sources are csrc/window.h's for 256-bit scalars
+// (Regs = shift registers; the kernels keep one byte per window in LDS: WinLds, wj26.h WjLds, glv26.h GlvLds); the table accessor is
+// ed28.h's TabStrided (host check, round-3 layout) or TabSlab (per-wave slab, row addresses formed at the access).
+template <int W, int BITS> using WnRegs = WinRegs<W, BITS, 4>;      // 65 windows of 4 bits (260), 86 of 3 bits (258)
 struct WnTabStrided {
     uint64_t* tab;
     size_t tstride;

@@ -132,11 +132,8 @@ __global__ __launch_bounds__(64) void k_wn_table_affine(WnAffWs ws, size_t L, in
 
 template <class F, bool JAC, int TAG>
 void wn_table_affine(const WnAffWs& ws, hipStream_t s) {
-    size_t r = (ws.m + 65535) / 65536, rmax = (size_t)(32 / ws.ne);
-    if (r > rmax) r = rmax;
-    if (r < 1) r = 1;
-    const size_t L = (ws.m + r - 1) / r;
-    k_wn_table_affine<F, JAC, TAG><<<(unsigned)((L + 63) / 64), 64, 0, s>>>(ws, L, (int)r);
+    const auto [L, rounds] = shared_inv_rounds(ws.m, (size_t)(32 / ws.ne));
+    k_wn_table_affine<F, JAC, TAG><<<(unsigned)((L + 63) / 64), 64, 0, s>>>(ws, L, rounds);
 }
 
 // +- entry base + |m| - 1 of record t's affine table (m = 1..8; 0 leaves (0, 0)), all eight entries from base on read (wn26.h lookup),

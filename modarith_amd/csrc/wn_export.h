@@ -106,25 +106,13 @@ __global__ __launch_bounds__(64) void k_wn_export(WnExpWs ws, size_t L, int roun
             xw[K] &= keep;
             yw[K] = (yw[K] & keep) | (K == 0 ? (1u & ~keep) : 0u);
         });
-        const size_t t = first + e;
-        if (xb) store_be_record<P>(xb, t, xw);
-        if (yb) store_be_record<P>(yb, t, yw);
-        if (sign) sign[t] = !yb ? (int)(yw[0] & 1) : (!xb ? (int)(xw[0] & 1) : 0);
+        store_affine_be<P>(xb, yb, sign, first + e, xw, yw);
     }
 }
 
-inline void wnexp_rounds(size_t m, size_t* L, int* rounds) {
-    size_t r = (m + 65535) / 65536;
-    if (r > 32) r = 32;
-    if (r < 1) r = 1;
-    *rounds = (int)r;
-    *L = (m + r - 1) / r;
-}
 template <class F, class P, int TAG>
 void wn_export(const WnExpWs& ws, unsigned char* x, unsigned char* y, int* sign, size_t first, hipStream_t s) {
-    size_t L;
-    int rounds;
-    wnexp_rounds(ws.m, &L, &rounds);
+    const auto [L, rounds] = shared_inv_rounds(ws.m);
     k_wn_export<F, P, TAG><<<(unsigned)((L + 63) / 64), 64, 0, s>>>(ws, L, rounds, x, y, sign, first);
 }
 

@@ -197,6 +197,39 @@ def test_fused_weierstrass_scalars_of_the_exceptional_cases(fx):
         assert torch.equal(x3, w2x) and torch.equal(y3, w2y)
 
 
+@pytest.mark.parametrize("name", ["ED25519", "ED448"])
+def test_straus_form_scalars_at_the_digit_edges(name):
+    """The Straus forms (csrc/ed26s.h, ed28s.h) take their signed 4-bit digits from csrc/window.h: the scalars where that recoding has
+    something to get wrong -- single digits d << 4i for d in {1, 7, 8, 9, 15} (8 is where the digit turns negative and carries into
+    the next window) at the bottom two and the top two windows of the record, 0, all-ones, 0x77..7, 0x88..8, the group order and its
+    neighbours -- each as e and as f, on two random projective points and the neutral element: mul2_get against mul2 + get.  One batch
+    of 175 records: two full waves and a ragged third."""
+    import torch
+    from modarith_amd.edwards import Edwards
+    Ed = Edwards(name)
+    q = int(load_golden("edwards_%s.json" % name)["order"], 16)
+    nd = 2 * Ed.nbytes                                                  # 4-bit windows of a record
+    top = nd - 1
+    scalars = [d << (4 * i) for i in (0, 1, top - 1, top) for d in (1, 7, 8, 9, 15)]
+    scalars += [0, int("f" * nd, 16), int("7" * nd, 16), int("8" * nd, 16), q, q - 1, q + 1]
+    other = [scalars[(7 * i + 3) % len(scalars)] for i in range(len(scalars))]
+    gen = torch.Generator(device="cuda").manual_seed(57)
+    R = Ed.mul(torch.randint(0, 256, (2, Ed.nbytes), dtype=torch.uint8, device="cuda", generator=gen), Ed.gen(2))
+    R1, R2, O = R[:, :, 0:1], R[:, :, 1:2], Ed.inf(1)
+    recs = []                                                           # (e, f, P, Q)
+    for s, o in zip(scalars, other):
+        recs += [(s, o, R1, R2), (o, s, R1, R2), (s, s, R1, R2), (s, s, R2, R1), (s, o, O, R2), (o, s, R1, O)]
+    recs += [(s, s, O, O) for s in scalars[:13]]
+    assert len(recs) == 175
+    be = lambda v: v.to_bytes(Ed.nbytes, "big").hex()
+    e, f = dev_bytes(torch, [be(r[0]) for r in recs]), dev_bytes(torch, [be(r[1]) for r in recs])
+    P, Q = torch.cat([r[2] for r in recs], dim=2).contiguous(), torch.cat([r[3] for r in recs], dim=2).contiguous()
+    x, y, _ = Ed.mul2_get(e, P, f, Q)
+    wx, wy, _ = Ed.get(Ed.mul2(e, P, f, Q))
+    bad = [i for i in range(len(recs)) if not (torch.equal(x[i], wx[i]) and torch.equal(y[i], wy[i]))]
+    assert not bad, [(i, hex(recs[i][0]), hex(recs[i][1])) for i in bad[:8]]
+
+
 def test_fused_more_points_than_resident_lanes(fx):
     """the kernels hold one table slot per RESIDENT lane (131 072) and walk larger batches grid-stride, rebuilding the
     table in the same slot: 2 full passes + a ragged third one, against the two-call form"""

@@ -665,3 +665,69 @@ def test_unsigned_limb_fields_at_the_edges_of_their_ranges(tmp_path):
                     E, Fv, G, H = M - A - B, D + Cc, D - Cc, B - A
                     want = [E * Fv % p, G * H % p, Fv * G % p, E * H % p]
                 assert formula(F, what, P, flatQ) == want, (F.name, "Straus add_pc", what, sa, sb)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="needs hipcc (host compile of the HIP headers)")
+def test_window_digits_and_top_bit_on_host_against_python_integers(tmp_path):
+    """csrc/window.h and take_top_bit of csrc/field.h as a stand-alone host program (tools/window_host.hip, under the address and
+    undefined-behaviour sanitizers), for the four parameter sets in use and for both WinRegs and WinLds::fill (into a plain array
+    standing in for the LDS column): with COUNT windows, sum_i (window(i) - 2^(W-1)) * 2^(W (COUNT-1-i)) == e and every window lies
+    in [0, 2^W).  Scalars: 0, 1, 2^(W-1) - 1, 2^(W-1), 2^(W-1) + 1; every single digit d << (W i), d in {1, 2^(W-1) - 1, 2^(W-1),
+    2^W - 1}; 0x77..7, 0x88..8 and all-ones cut (from the top, digit by digit) to the admissible range; the largest admissible value;
+    10^4 seeded random ones.  Admissible: e <= min(2^(64 NI) - 1, 2^BITS - 1 - bias) -- every 256- and 448-bit scalar, and about
+    1.87 * 2^130 for the halves of the secp256k1 split (which guarantees 2^128).  take_top_bit<4> / <7>: the bits it hands out and the
+    words after the first call, against Python shifts on the same patterns."""
+    import random
+    exe = str(tmp_path / "window_host")
+    cc = HIPCC if os.path.exists(HIPCC) else "hipcc"
+    subprocess.run([cc, "-O1", "-g", "-std=c++17", "-w", "--offload-host-only", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tools", "window_host.hip"), "-o", exe], check=True, timeout=900)
+    rng = random.Random(29)
+    sets = [(4, 260, 4), (3, 258, 4), (4, 452, 7), (4, 132, 3)]
+    asked, lines = [], []
+    for si, (W, BITS, NI) in enumerate(sets):
+        count, half = BITS // W, 1 << (W - 1)
+        bias = sum(half << (W * i) for i in range(count))
+        top = min(2**(64 * NI) - 1, 2**BITS - 1 - bias)
+        if (W, BITS, NI) != (4, 132, 3):
+            assert top == 2**(64 * NI) - 1                                      # every scalar of NI words
+        else:
+            assert 2**128 < top and abs(top / 2**130 - 1.87) < 0.01
+
+        def cut(digit):                                                         # 0xdd..d with as many digits as stay admissible
+            k = 16 * NI
+            while int(digit * k, 16) > top:
+                k -= 1
+            return int(digit * k, 16)
+        es = [0, 1, half - 1, half, half + 1]
+        es += [d << (W * i) for i in range(count) for d in (1, half - 1, half, 2 * half - 1) if d << (W * i) <= top]
+        es += [cut("7"), cut("8"), cut("f"), top]
+        es += [rng.randint(0, top) for _ in range(10**4)]
+        for e in es:
+            asked.append(("w", si, e))
+            lines.append("w %d %x" % (si, e))
+    for NW in (4, 7):
+        full = 2**(64 * NW) - 1
+        vs = [0, 1, full, int("7" * (16 * NW), 16), int("8" * (16 * NW), 16)] + [1 << i for i in range(64 * NW)]
+        vs += [rng.randint(0, full) for _ in range(1000)]
+        for v in vs:
+            asked.append(("t", NW, v))
+            lines.append("t %d %x" % (NW, v))
+    p = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
+    out = p.stdout.splitlines()
+    assert len(out) == len(asked)
+    for (kind, which, v), line in zip(asked, out):
+        if kind == "w":
+            W, BITS, NI = sets[which]
+            count, half = BITS // W, 1 << (W - 1)
+            regs, lds, written = line.split()
+            assert int(written) == count, (which, hex(v))
+            for digits in (regs, lds):
+                wins = [int(c, 16) for c in digits]
+                assert len(wins) == count and all(0 <= w < 2 * half for w in wins), (which, hex(v), digits)
+                assert sum((w - half) << (W * (count - 1 - i)) for i, w in enumerate(wins)) == v, (which, hex(v), digits)
+        else:
+            bits, first = line.split()
+            assert bits == format(v, "0%db" % (64 * which)), (which, hex(v))
+            assert int(first, 16) == (v << 1) & (2**(64 * which) - 1), (which, hex(v))

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""The kernels of the units that see the fixed-base comb (csrc/comb.h), for "is it the same code" between two built trees.
+"""The kernels of a list of units, for "is it the same code" between two built trees.
 
   python tools/comb_objects.py --tree TREE --out figures.json           # TREE: a checkout on which build() has run
   python tools/comb_objects.py --pair PARENT.json NEW.json --out profiles/comb_one_walk.json
 
-Per kernel of the G units (which instantiate the walk) and of the F / F2 units (which only include ed26.h, ed28.h, wn26.h, wj26.h or
-glv26.h): the resource figures of tools/kernel_resources.py, the instruction count, a hash of the instruction text as
+--units A,B,...: the objects to read, by default the units that see the fixed-base comb (csrc/comb.h): the G units, which instantiate
+the walk, and the F / F2 units, which only include ed26.h, ed28.h, wn26.h, wj26.h or glv26.h.  A name is an object of
+modarith_amd/build/ (capi_X25519, capi_ED25519_part2); one with a slash is relative to modarith_amd/ (plugins/capi_ladder_M383, a
+generated ladder).  --pair compares the units its two files hold.
+
+Per kernel: the resource figures of tools/kernel_resources.py, the instruction count, a hash of the instruction text as
 tools/chain_objects.py takes it, and the loop-weighted instruction and multiply-add counts of tools/isa_mix.py; per tree `nm -D` of the
 library.  No GPU needed.
 """
@@ -41,10 +45,10 @@ def latch_trips(code):
     return out
 
 
-def figures(tree):
+def figures(tree, units=UNITS):
     out = {}
-    for u in UNITS:
-        obj = os.path.join(tree, "modarith_amd", "build", u + ".o")
+    for u in units:
+        obj = os.path.join(tree, "modarith_amd", *(u.split("/") if "/" in u else ("build", u))) + ".o"
         code = {nm: c for (_, nm), c in isa_mix.kernels(obj, "*").items()}
         ks = {}
         for k in kernel_resources.kernels_of(obj):
@@ -61,7 +65,9 @@ def figures(tree):
 
 def pair(parent, new):
     units, differs = {}, []
-    for u in UNITS:
+    assert set(parent) == set(new), sorted(set(parent) ^ set(new))
+    names = sorted(u for u in parent if u != "nm_D")
+    for u in names:
         kp, kn = parent[u], new[u]
         assert set(kp) == set(kn), (u, sorted(set(kp) ^ set(kn)))
         units[u] = {}
@@ -73,18 +79,19 @@ def pair(parent, new):
                 differs.append({"unit": u, "kernel": nm, "parent_to_new": {x: [kp[nm][x], kn[nm][x]] for x in kp[nm] if x != "isa_sha256" and kp[nm][x] != kn[nm][x]},
                                 "no_figure_higher": all(kn[nm][x] <= kp[nm][x] for x in kp[nm] if x != "isa_sha256")})
     return {"units": units, "kernels": sum(len(v) for v in units.values()), "kernels_whose_instruction_text_differs": differs,
-            "units_without_any_difference": [u for u in UNITS if all(k["same_as_parent"] for k in units[u].values())],
+            "units_without_any_difference": [u for u in names if all(k["same_as_parent"] for k in units[u].values())],
             "nm_D_equal_but_for_hip_cuid": parent["nm_D"] == new["nm_D"], "nm_D_symbols": len(new["nm_D"])}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tree", default=kernel_resources.ROOT)
+    ap.add_argument("--units", default=",".join(UNITS), help="comma-separated objects (see above); default: the G / F / F2 units")
     ap.add_argument("--pair", nargs=2, default=None, metavar=("PARENT", "NEW"))
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     load = lambda p: json.load(open(p))
-    out = pair(*map(load, args.pair)) if args.pair else figures(os.path.abspath(args.tree))
+    out = pair(*map(load, args.pair)) if args.pair else figures(os.path.abspath(args.tree), args.units.split(","))
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
     return 0

@@ -103,7 +103,7 @@ static void nist_kP(const uint64_t* ew, const uint64_t* X, const uint64_t* Y, co
     ma::wn_table_affine_lane<ma::Fm26, true>(ws, 1, 1, 0);
     uint64_t k[4];
     ma::Wj26::reduce_scalar(ew, k);
-    ma::WnRegs<4, 260> dig;
+    ma::WjRegs dig;
     dig.init(k);
     ma::Wj26::mul_acc_aff(dig, ws, 0, R);
 }
@@ -140,7 +140,7 @@ extern "C" void nist256_jac_mul2_get_host(const uint64_t* ew, const uint64_t* PX
     ma::Wj26::table_of(nist_cp(PX, PY, PZ), ws, 0, 0);
     ma::Wj26::table_of(nist_cp(QX, QY, QZ), ws, 0, 8);
     ma::wn_table_affine_lane<ma::Fm26, true>(ws, 1, 1, 0);
-    ma::WnRegs<4, 260> de, df;
+    ma::WjRegs de, df;
     de.init(ew);
     df.init(fw);
     ma::Wj26::Pt R;
