@@ -134,7 +134,7 @@ extern "C" int ecn_ed25519_mulgen_get_batch(const char* e, char* x, char* y, int
             k_ed25519_mulgen<true><<<(unsigned)((m + 63) / 64), 64, 0, s>>>(eb, xb, yb, sign, first, m, Ed26lWs(nullptr, m));
         }
     }
-    return check_launch("ecn mulgen_get");
+    return check_launch(ws.p ? "ecn mulgen_get" : "ecn mulgen_get (self-contained)");
 }
 
 // bv = [bk](9): rfc7748(bk, base, bv) of rfc7748.c:297-333 for a batch of private keys, on the fixed-base table

@@ -161,7 +161,7 @@ extern "C" int ecn_ed448_mulgen_get_batch(const char* e, char* x, char* y, int* 
             k_ed448_mulgen<true><<<(unsigned)((m + 63) / 64), 64, 0, s>>>(eb, xb, yb, sign, first, m, Ed28lWs(nullptr, m));
         }
     }
-    return check_launch("ecn mulgen_get");
+    return check_launch(ws.p ? "ecn mulgen_get" : "ecn mulgen_get (self-contained)");
 }
 
 // bv = [bk](5): rfc7748(bk, base, bv) for a batch of private keys, on the fixed-base table of ED448 (4-isogenous to curve448)
@@ -183,5 +183,5 @@ extern "C" int rfc7748_X448_base_batch(const char* bk, char* bv, size_t n, void*
             k_x448_base<true><<<(unsigned)((m + 63) / 64), 64, 0, s>>>(kb, vb, first, m, Ed28lWs(nullptr, m));
         }
     }
-    return check_launch("rfc7748 base");
+    return check_launch(ws.p ? "rfc7748 base" : "rfc7748 base (self-contained)");
 }

@@ -124,5 +124,5 @@ extern "C" int ecn_secp256k1_mulgen_get_batch(const char* e, char* x, char* y, i
     const size_t lanes = ((n + MULGEN_G - 1) / MULGEN_G + 63) / 64 * 64, cap = (size_t)4 * 1024 * 64;       // MULGEN_G scalars per lane; at most 4 waves on each of the 1024 SIMDs
     k_secp256k1_mulgen_get<<<(unsigned)((lanes < cap ? lanes : cap) / 64), 64, 0, (hipStream_t)st>>>(
         reinterpret_cast<const unsigned char*>(e), reinterpret_cast<unsigned char*>(x), reinterpret_cast<unsigned char*>(y), sign, n);
-    return check_launch("ecn mulgen_get");
+    return check_launch("ecn mulgen_get (self-contained)");
 }

@@ -40,9 +40,11 @@ def test_edge_protocol_gpu(P):
 
 @pytest.mark.parametrize("name", ["NIST256", "SECP256K1", "ED25519"])
 def test_mulgen_get_second_grid_stride_pass(name):
-    """the fixed-base kernels give each lane four scalars and cap the grid at 262144 lanes: with n = 4 * 262144 + 77 the
-    grid-stride loop runs a second (partial) pass, which the suite's other sizes never reach.  Checked against the general
-    fused kernel on the generator, record by record."""
+    """the eager mulgen_get at n = 4 * 262144 + 77 against the general fused kernel on the generator, record by record.  Since round 5
+    the eager call runs the one-scalar-per-lane kernels (k_<c>_mulgen and the shared export, in chunks), so this is a check of those at
+    just over 2^20 records.  The kernels the size was chosen for -- four scalars per lane, a grid capped at 262144 lanes, a second
+    (partial) grid-stride pass -- now run only without scratch, on a stream under capture:
+    tests/test_gpu_fixed_base_fallbacks.py::test_scratchless_mulgen_get_second_pass_and_chunk_boundary takes them through that pass."""
     import torch
     assert torch.cuda.is_available(), "these tests need the MI355X"
     from modarith_amd.edwards import Curve
