@@ -101,6 +101,23 @@ W32_ED_BATCH_FUNCS = tuple(f for f in ED_BATCH_FUNCS if f != "mul2_exact")      
 W32_ED_SCALAR_FUNCS = ED_SCALAR_FUNCS
 
 
+# ---- batched hashes (include/modarith_amd_hash.h): hash.c's names with _batch added, records given as parts
+class HashPart(ctypes.Structure):
+    """ma_hash_part"""
+    _fields_ = [("ptr", c_void_p), ("stride", c_size_t), ("lens", c_void_p), ("len", ctypes.c_uint32)]
+
+
+_HP = ctypes.POINTER(HashPart)
+_SIG_HASH = {
+    "HASH256_batch": [_HP, c_int, _P, c_size_t, c_size_t, _P],
+    "HASH384_batch": [_HP, c_int, _P, c_size_t, c_size_t, _P],
+    "HASH512_batch": [_HP, c_int, _P, c_size_t, c_size_t, _P],
+    "SHA3_hash_batch": [c_int, _HP, c_int, _P, c_size_t, c_size_t, _P],
+    "SHA3_shake_batch": [c_int, _HP, c_int, _P, c_size_t, c_size_t, c_size_t, _P],
+}
+HASH_FUNCS = tuple(_SIG_HASH)
+
+
 def _declare_curve(lib, C: str, funcs=ED_BATCH_FUNCS) -> None:
     """argtypes / restypes of the batched curve entry points ecn_<C>_*_batch of `lib` (the main library or a curve plug-in)"""
     g = lambda f: getattr(lib, "ecn_%s_%s" % (C, f))
@@ -200,6 +217,10 @@ def load() -> ctypes.CDLL:
         f = getattr(lib, "ecn_%s_mul2_get_workspace_bytes" % c)
         f.argtypes = [c_size_t]
         f.restype = c_size_t
+    for name, args in _SIG_HASH.items():
+        f = getattr(lib, name)
+        f.argtypes = args
+        f.restype = c_int
     lib.modarith_amd_last_error.restype = c_char_p
     lib.modarith_amd_abi_version.restype = c_int
     lib.modarith_amd_device_count.restype = c_int
