@@ -24,6 +24,7 @@
 namespace ma {
 
 struct Fe26 {
+    using limb = uint32_t; static constexpr int NLIMB = 10;      // (shared_inv.h)
     static constexpr uint32_t M26 = (1u << 26) - 1, M25 = (1u << 25) - 1;
     // bit position of limb i
     static constexpr int pos(int i) { return (51 * i + 1) / 2; }   // 0,26,51,77,102,128,153,179,204,230
@@ -173,6 +174,7 @@ struct Fe26 {
     }
     static MA_DEV void copy(const uint32_t* f, uint32_t* r) { static_for<0, 10>([&](auto I) { r[I] = f[I]; }); }
     static MA_DEV void set(uint32_t v, uint32_t* r) { static_for<0, 10>([&](auto I) { r[I] = (I == 0) ? v : 0u; }); }
+    static MA_DEV void set_one(uint32_t* r) { set(1, r); }
 
     static MA_DEV void sqn(uint32_t* f, int n) {
 #pragma unroll 1

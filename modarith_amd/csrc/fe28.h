@@ -19,6 +19,7 @@
 namespace ma {
 
 struct Fe28 {
+    using limb = uint32_t; static constexpr int NLIMB = 16;      // (shared_inv.h)
     static constexpr uint32_t M28 = (1u << 28) - 1;
 
     // fold the 31 raw columns (2^448 = 2^224 + 1) and carry to tight limbs
@@ -255,6 +256,7 @@ struct Fe28 {
     }
     static MA_DEV void copy(const uint32_t* f, uint32_t* r) { static_for<0, 16>([&](auto I) { r[I] = f[I]; }); }
     static MA_DEV void set(uint32_t v, uint32_t* r) { static_for<0, 16>([&](auto I) { r[I] = (I == 0) ? v : 0u; }); }
+    static MA_DEV void set_one(uint32_t* r) { set(1, r); }
     static MA_DEV void sqn(uint32_t* f, int n) {                    // f tight (results of mul / sqr)
 #pragma unroll 1
         for (int i = 0; i < n; i++) sqr_k(f, f);

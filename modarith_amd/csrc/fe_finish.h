@@ -6,64 +6,71 @@
 // owe one inversion to each lane: a first kernel (k_x25519_fe26_xz / k_x448_fe28_xz) runs the ladders and leaves canonical
 // x2 in the output record and canonical z2 in a workspace; the second (k_fe_finish) gives lane j the elements
 // {r * L + j : r < rounds} (L lanes, so that every access of a wave is one coalesced row), multiplies their z up into
-// prefix products, inverts the last one, and walks back with three multiplications per element.  A z2 of zero (u = 0, the
-// low-order points of RFC 7748 section 7) would annihilate the whole product: it is replaced by 1 on the way in and its
-// output -- x2 * 0^(p-2) = 0 in the reference -- is set to zero on the way out, by a per-lane mask (v_cndmask on the way in,
-// v_and on the way out; field.h lane_mask()), never by a branch.  Same bytes as the one-inversion-per-lane kernels for every input.
+// prefix products, inverts the last one, and walks back with three multiplications per element (shared_inv.h: the walk).  A z2 of
+// zero (u = 0, the low-order points of RFC 7748 section 7) enters the product as 1 and its output -- x2 * 0^(p-2) = 0 in the
+// reference -- leaves as zero, by a select and a per-lane mask.  Same bytes as the one-inversion-per-lane kernels for every input.
 #pragma once
-#include "field.h"
+#include "shared_inv.h"
 
 namespace ma {
 
-template <class F, int NL, int NW>
-struct FeFinish {
-    // z words of element e (canonical, as the first kernel left them), with 0 -> 1; returns the zero flag
-    static MA_DEV bool load_z(const uint64_t* wz, size_t n, size_t e, bool valid, uint32_t* z) {
-        uint64_t zw[NW];
-        static_for<0, NW>([&](auto K) { zw[K] = (K == 0) ? 1 : 0; });
-        if (valid) static_for<0, NW>([&](auto K) { zw[K] = wz[(size_t)K * n + e]; });
-        uint64_t any = 0;
-        static_for<0, NW>([&](auto K) { any |= zw[K]; });
+// The items of lane j for shared_inv_walk(): elements r * L + j < n, canonical denominators A[NW][n] (word-major, as the kernel in front
+// left them), prefix products wc[NL][n] (limb-major, 32-bit), NUM numerators: num(Q, K, e) = word K of numerator Q of element e, and
+// sink(e, q0, q1) takes the canonical quotients (q1 = q0 where NUM = 1), all zero where the denominator was zero
+template <class F, int NL, int NW, int NUM, class NUMS, class SINK>
+struct FeDivItems {
+    const uint64_t* A;
+    uint32_t* wc;
+    size_t n, L, j;
+    const NUMS& num;
+    SINK& sink;
+    MA_DEV size_t element(int r) const { return (size_t)r * L + j; }
+    MA_DEV bool valid(int r) const { return element(r) < n; }
+    MA_DEV bool load_den(int r, uint32_t* z) const {
+        const size_t e = element(r);
+        uint64_t zw[NW], any = 0;
+        static_for<0, NW>([&](auto K) { any |= zw[K] = A[(size_t)K * n + e]; });
         const bool zero = any == 0;
         zw[0] = zero ? 1 : zw[0];
         F::from_words(zw, z);
         return zero;
     }
-    static MA_DEV void run(uint64_t* bv, const uint64_t* wz, uint32_t* wc, size_t n, size_t L, int rounds, size_t j) {
-        uint32_t c[NL], z[NL];
-        F::set(1, c);
-#pragma unroll 1
-        for (int r = 0; r < rounds; r++) {
-            const size_t e = (size_t)r * L + j;
-            const bool valid = e < n;
-            (void)load_z(wz, n, e, valid, z);
-            F::mul(c, z, c);
-            if (valid) static_for<0, NL>([&](auto I) { wc[(size_t)I * n + e] = c[I]; });
-        }
-        uint32_t inv[NL];
-        F::invert(c, inv);
-#pragma unroll 1
-        for (int r = rounds - 1; r >= 0; r--) {
-            const size_t e = (size_t)r * L + j;
-            if (e >= n) continue;                                   // (its z counted as 1: nothing to undo)
-            uint32_t zinv[NL], x[NL];
-            const uint64_t keep = lane_mask(!load_z(wz, n, e, true, z));     // (field.h: an opaque mask, not a select)
-            if (r > 0) {
-                uint32_t cp[NL];
-                const size_t e1 = e - L;
-                static_for<0, NL>([&](auto I) { cp[I] = wc[(size_t)I * n + e1]; });
-                F::mul(inv, cp, zinv);
-                F::mul(inv, z, inv);
-            } else {
-                F::copy(inv, zinv);
-            }
-            uint64_t xw[NW], ow[NW];
-            static_for<0, NW>([&](auto K) { xw[K] = bv[e * NW + K]; });
+    MA_DEV void store_prefix(int r, const uint32_t* c) const {
+        static_for<0, NL>([&](auto I) { wc[(size_t)I * n + element(r)] = c[I]; });
+    }
+    // the walk asks for r = i - 1 while it is at element(i): element(r + 1) is that index, already in registers, and one subtraction
+    // gives this one; written as element(r) the compiler forms r L + j again (a second v_mad_u64_u32 per item in every instance)
+    MA_DEV void load_prefix(int r, uint32_t* c) const {
+        const size_t e = element(r + 1) - L;
+        static_for<0, NL>([&](auto I) { c[I] = wc[(size_t)I * n + e]; });
+    }
+    MA_DEV void emit(int r, const uint32_t* zinv, bool zero) const {
+        const size_t e = element(r);
+        const uint64_t keep = lane_mask(!zero);
+        uint64_t q[NUM][NW];
+        static_for<0, NUM>([&](auto Q) {
+            uint64_t xw[NW];
+            uint32_t x[NL];
+            static_for<0, NW>([&](auto K) { xw[K] = num(Q, K, e); });
             F::from_words(xw, x);
             F::mul(x, zinv, x);
-            F::to_words(x, ow);
-            static_for<0, NW>([&](auto K) { bv[e * NW + K] = ow[K] & keep; });
-        }
+            F::to_words(x, q[Q]);
+        });
+        static_for<0, NUM>([&](auto Q) { static_for<0, NW>([&](auto K) { q[Q][K] &= keep; }); });
+        sink(e, q[0], q[NUM - 1]);
+    }
+};
+template <class F, int NL, int NW, int NUM, class NUMS, class SINK>
+MA_DEV void fe_div_lane(const uint64_t* A, uint32_t* wc, size_t n, size_t L, int rounds, size_t j, const NUMS& num, SINK& sink) {
+    shared_inv_walk<F>(rounds, FeDivItems<F, NL, NW, NUM, NUMS, SINK>{A, wc, n, L, j, num, sink});
+}
+
+// the ladders: x2 in the output record bv[n][NW], divided in place
+template <class F, int NL, int NW>
+struct FeFinish {
+    static MA_DEV void run(uint64_t* bv, const uint64_t* wz, uint32_t* wc, size_t n, size_t L, int rounds, size_t j) {
+        auto sink = [&](size_t e, const uint64_t* q, const uint64_t*) { static_for<0, NW>([&](auto K) { bv[e * NW + K] = q[K]; }); };
+        fe_div_lane<F, NL, NW, 1>(wz, wc, n, L, rounds, j, [&](int, int K, size_t e) { return bv[e * NW + K]; }, sink);
     }
 };
 
@@ -76,52 +83,12 @@ __global__ __launch_bounds__(256) void k_fe_finish(uint64_t* bv, const uint64_t*
 
 // ---- round 5: the same trick with TWO numerators per denominator, for the ladder form of the fused Edwards multiplications
 // (ed26l.h: u = nu / D and w = nw / D in front of the ladder, x = X / Z and y = Y / Z behind it).  A, B, C: canonical words,
-// word-major [NW][n] (every access of a wave is one coalesced row).  B[e] <- B[e] / A[e], C[e] <- C[e] / A[e] handed to a SINK:
-//   sink(e, bw, cw)                 bw, cw = the canonical quotients (zero where A[e] was zero)
+// word-major [NW][n] (every access of a wave is one coalesced row).  B[e] / A[e], C[e] / A[e] are handed to sink(e, bw, cw).
 template <class F, int NL, int NW>
 struct FeBatchDiv {
-    using Z = FeFinish<F, NL, NW>;
     template <class SINK>
     static MA_DEV void run(const uint64_t* A, const uint64_t* B, const uint64_t* Cn, uint32_t* wc, size_t n, size_t L, int rounds, size_t j, SINK& sink) {
-        uint32_t c[NL], z[NL];
-        F::set(1, c);
-#pragma unroll 1
-        for (int r = 0; r < rounds; r++) {
-            const size_t e = (size_t)r * L + j;
-            const bool valid = e < n;
-            (void)Z::load_z(A, n, e, valid, z);
-            F::mul(c, z, c);
-            if (valid) static_for<0, NL>([&](auto I) { wc[(size_t)I * n + e] = c[I]; });
-        }
-        uint32_t inv[NL];
-        F::invert(c, inv);
-#pragma unroll 1
-        for (int r = rounds - 1; r >= 0; r--) {
-            const size_t e = (size_t)r * L + j;
-            if (e >= n) continue;                                   // (its denominator counted as 1: nothing to undo)
-            uint32_t zinv[NL], x[NL];
-            const uint64_t keep = lane_mask(!Z::load_z(A, n, e, true, z));
-            if (r > 0) {
-                uint32_t cp[NL];
-                const size_t e1 = e - L;
-                static_for<0, NL>([&](auto I) { cp[I] = wc[(size_t)I * n + e1]; });
-                F::mul(inv, cp, zinv);
-                F::mul(inv, z, inv);
-            } else {
-                F::copy(inv, zinv);
-            }
-            uint64_t xw[NW], bw[NW], cw[NW];
-            static_for<0, NW>([&](auto K) { xw[K] = B[(size_t)K * n + e]; });
-            F::from_words(xw, x);
-            F::mul(x, zinv, x);
-            F::to_words(x, bw);
-            static_for<0, NW>([&](auto K) { xw[K] = Cn[(size_t)K * n + e]; });
-            F::from_words(xw, x);
-            F::mul(x, zinv, x);
-            F::to_words(x, cw);
-            static_for<0, NW>([&](auto K) { bw[K] &= keep; cw[K] &= keep; });
-            sink(e, bw, cw);
-        }
+        fe_div_lane<F, NL, NW, 2>(A, wc, n, L, rounds, j, [&](int Q, int K, size_t e) { return (Q == 0 ? B : Cn)[(size_t)K * n + e]; }, sink);
     }
 };
 // TAG keeps the instantiations of different translation units apart (one code object each)

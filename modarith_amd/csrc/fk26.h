@@ -16,6 +16,7 @@
 namespace ma {
 
 struct Fk26 {
+    using limb = int32_t; static constexpr int NLIMB = 10;      // (shared_inv.h)
     static constexpr int32_t M26 = (1 << 26) - 1;
     static constexpr int32_t FC = 0x3d10;             // 2^260 mod p = 2^36 + FC
     static constexpr int32_t prime(int i) {           // canonical digits of p

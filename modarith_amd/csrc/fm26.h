@@ -26,6 +26,7 @@
 namespace ma {
 
 struct Fm26 {
+    using limb = int32_t; static constexpr int NLIMB = 10;      // (shared_inv.h)
     static constexpr int32_t M26 = (1 << 26) - 1;
     static constexpr int32_t P8 = 0x3ff0000;     // digit 8 of p in the all-positive form: B - 2^16
     static constexpr int32_t P9 = 0x3fffff;      // digit 9: 2^22 - 1

@@ -16,6 +16,7 @@
 #pragma once
 #include "capi_common.h"
 #include "kernels.h"
+#include "shared_inv.h"
 
 namespace ma {
 
@@ -48,80 +49,51 @@ struct WnAffWs {
     }
 };
 
-// lane j of L: the ne entries of records j, j + L, ..., j + (R - 1) L -- up to 32 entries under one inversion.  flag[t]: bit 0 = the
+// The items of lane j for shared_inv_walk() (shared_inv.h): the ne entries of records j, j + L, ..., j + (R - 1) L -- up to 32 entries
+// under one inversion --, item g = entry g % ne of record (g / ne) L + j, its Z the denominator; (x, y) go back into the entry.  An entry
+// with Z = 0 keeps the X, Y it has (nobody reads it).  flag[t], written on the way down (entry 8 comes before entry 0): bit 0 = the
 // first table's point is at infinity (its entry 1 has Z = 0; then all its multiples have), bit 1 = the second table's (entries 8..15)
 template <class F, bool JAC>
-MA_DEV void wn_table_affine_lane(const WnAffWs& ws, size_t L, int R, size_t j) {
-    int32_t c[10], z[10], one[10];
-    F::set_one(one);
-    F::set_one(c);
-    const int ne = ws.ne;
-#pragma unroll 1
-    for (int g = 0; g < ne * R; g++) {
-        const int e = g % ne;
-        const size_t t = (size_t)(g / ne) * L + j;
-        if (t >= ws.m) continue;
-        ws.load<F>(e, 2, t, z);
-        uint64_t zw[4];
-        F::to_words(z, zw);
-        const bool z0 = (zw[0] | zw[1] | zw[2] | zw[3]) == 0;
-        if (e == 0) ws.flag[t] = z0 ? 1u : 0u;
-        if (e == 8) ws.flag[t] |= z0 ? 2u : 0u;
-        F::select(z0, z, one, z);
-        F::mul(c, z, c);
+struct WnAffItems {
+    const WnAffWs& ws;
+    size_t L, j;
+    MA_DEV int entry(int g) const { return g % ws.ne; }
+    MA_DEV size_t record(int g) const { return (size_t)(g / ws.ne) * L + j; }
+    MA_DEV bool valid(int g) const { return record(g) < ws.m; }
+    MA_DEV bool load_den(int g, int32_t* z) const {
+        ws.load<F>(entry(g), 2, record(g), z);
+        return den_or_one<F>(z);
+    }
+    MA_DEV void store_prefix(int g, const int32_t* c) const {
         uint64_t w[5];
         F::pack(c, w);
-        static_for<0, 5>([&](auto K) { ws.C[(size_t)(e * 5 + K) * ws.m + t] = w[K]; });
+        static_for<0, 5>([&](auto K) { ws.C[(size_t)(entry(g) * 5 + K) * ws.m + record(g)] = w[K]; });
     }
-    int32_t inv[10];
-    F::invert(c, inv);
-#pragma unroll 1
-    for (int g = ne * R - 1; g >= 0; g--) {
-        const int e = g % ne;
-        const size_t t = (size_t)(g / ne) * L + j;
-        if (t >= ws.m) continue;                                    // (counted as 1 above: nothing to undo)
-        int32_t zi[10], x[10];
-        ws.load<F>(e, 2, t, z);
-        // the SAME test as on the way up, entry by entry: what counted as 1 there must count as 1 here.  flag[t] only says that entry 0 /
-        // entry 8 is at infinity; an input off the curve -- (x, 0, Z != 0): its doubling has Z3 = 2 Y Z = 0 -- has Z = 0 in entries 2P, 4P,
-        // 6P, 8P alone, and taking their Z = 0 into `inv` here zeroed the tables of every record EARLIER in this lane's column (round-5
-        // advisor: one unvalidated public key in a verification batch spoiled up to three other records).  A record off the curve still
-        // means nothing itself; it no longer touches its neighbours.
-        uint64_t zw[4];
-        F::to_words(z, zw);
-        const bool z0 = (zw[0] | zw[1] | zw[2] | zw[3]) == 0;
-        F::select(z0, z, one, z);
-        if (g > 0) {
-            const int ep = (g - 1) % ne;
-            const size_t tp = (size_t)((g - 1) / ne) * L + j;
-            uint64_t w[5];
-            int32_t cp[10];
-            static_for<0, 5>([&](auto K) { w[K] = ws.C[(size_t)(ep * 5 + K) * ws.m + tp]; });
-            F::unpack(w, cp);
-            F::mul(inv, cp, zi);
-            F::mul(inv, z, inv);
-        } else {
-            F::copy(inv, zi);
-        }
-        if constexpr (JAC) {
-            int32_t zi2[10];
-            F::sqr(zi, zi2);
-            ws.load<F>(e, 0, t, x);
-            F::mul(x, zi2, x);
-            ws.store<F>(e, 0, t, x);
-            F::mul(zi2, zi, zi2);
-            ws.load<F>(e, 1, t, x);
-            F::mul(x, zi2, x);
-            ws.store<F>(e, 1, t, x);
-        } else {
-            ws.load<F>(e, 0, t, x);
-            F::mul(x, zi, x);
-            ws.store<F>(e, 0, t, x);
-            ws.load<F>(e, 1, t, x);
-            F::mul(x, zi, x);
-            ws.store<F>(e, 1, t, x);
-        }
+    MA_DEV void load_prefix(int g, int32_t* c) const {
+        uint64_t w[5];
+        static_for<0, 5>([&](auto K) { w[K] = ws.C[(size_t)(entry(g) * 5 + K) * ws.m + record(g)]; });
+        F::unpack(w, c);
     }
+    MA_DEV void emit(int g, const int32_t* zi, bool zero) const {
+        const int e = entry(g);
+        const size_t t = record(g);
+        if (e == 8) ws.flag[t] = zero ? 2u : 0u;
+        if (e == 0) ws.flag[t] = (ws.ne > 8 ? ws.flag[t] : 0u) | (zero ? 1u : 0u);
+        int32_t x[10], zx[10];
+        if constexpr (JAC) F::sqr(zi, zx);
+        else F::copy(zi, zx);
+        ws.load<F>(e, 0, t, x);
+        F::mul(x, zx, x);
+        ws.store<F>(e, 0, t, x);
+        if constexpr (JAC) F::mul(zx, zi, zx);
+        ws.load<F>(e, 1, t, x);
+        F::mul(x, zx, x);
+        ws.store<F>(e, 1, t, x);
+    }
+};
+template <class F, bool JAC>
+MA_DEV void wn_table_affine_lane(const WnAffWs& ws, size_t L, int R, size_t j) {
+    shared_inv_walk<F>(ws.ne * R, WnAffItems<F, JAC>{ws, L, j});
 }
 
 template <class F, bool JAC, int TAG>

@@ -15,6 +15,7 @@
 #pragma once
 #include "capi_common.h"
 #include "kernels.h"
+#include "shared_inv.h"
 
 namespace ma {
 
@@ -53,61 +54,52 @@ struct WnExpWs {
     }
 };
 
-// lane j of L: records j, j + L, j + 2L, ... of the chunk
-template <class F, class P, int TAG>
-__global__ __launch_bounds__(64) void k_wn_export(WnExpWs ws, size_t L, int rounds, unsigned char* xb, unsigned char* yb, int* sign, size_t first) {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= L) return;
-    int32_t c[10], z[10], one[10];
-    F::set_one(one);
-    F::set_one(c);
-#pragma unroll 1
-    for (int r = 0; r < rounds; r++) {
-        const size_t e = (size_t)r * L + j;
-        if (e >= ws.m) continue;
-        ws.load<F>(ws.Z, e, z);
-        uint64_t zw[4];
-        F::to_words(z, zw);
-        const bool z0 = (zw[0] | zw[1] | zw[2] | zw[3]) == 0;
-        F::select(z0, z, one, z);
-        F::mul(c, z, c);
+// The items of lane j for shared_inv_walk() (shared_inv.h): records j, j + L, j + 2L, ... of the chunk, Z the denominator, x = X / Z and
+// y = Y / Z as canonical words to sink(e, xw, yw); a record whose Z is zero mod p leaves as (0, 1)
+template <class F, class SINK>
+struct WnExportItems {
+    const WnExpWs& ws;
+    size_t L, j;
+    const SINK& sink;
+    MA_DEV size_t record(int r) const { return (size_t)r * L + j; }
+    MA_DEV bool valid(int r) const { return record(r) < ws.m; }
+    MA_DEV bool load_den(int r, int32_t* z) const {
+        ws.load<F>(ws.Z, record(r), z);
+        return den_or_one<F>(z);
+    }
+    MA_DEV void store_prefix(int r, const int32_t* c) const {
         uint64_t w[5];
         F::pack(c, w);
-        static_for<0, 5>([&](auto K) { ws.C[(size_t)K * ws.m + e] = w[K]; });
+        static_for<0, 5>([&](auto K) { ws.C[(size_t)K * ws.m + record(r)] = w[K]; });
     }
-    int32_t inv[10];
-    F::invert(c, inv);
-#pragma unroll 1
-    for (int r = rounds - 1; r >= 0; r--) {
-        const size_t e = (size_t)r * L + j;
-        if (e >= ws.m) continue;                                    // (its denominator counted as 1: nothing to undo)
-        int32_t zinv[10], x[10];
-        ws.load<F>(ws.Z, e, z);
-        uint64_t zw[4], xw[4], yw[4];
-        F::to_words(z, zw);
-        const bool z0 = (zw[0] | zw[1] | zw[2] | zw[3]) == 0;
-        F::select(z0, z, one, z);
-        if (r > 0) {
-            int32_t cp[10];
-            ws.load<F>(ws.C, e - L, cp);
-            F::mul(inv, cp, zinv);
-            F::mul(inv, z, inv);
-        } else {
-            F::copy(inv, zinv);
-        }
-        ws.load<F>(ws.X, e, x);
-        F::mul(x, zinv, x);
-        F::to_words(x, xw);
-        ws.load<F>(ws.Y, e, x);
-        F::mul(x, zinv, x);
-        F::to_words(x, yw);
-        const uint64_t keep = lane_mask(!z0);
+    MA_DEV void load_prefix(int r, int32_t* c) const { ws.load<F>(ws.C, record(r), c); }
+    MA_DEV void emit(int r, const int32_t* zinv, bool zero) const {
+        const size_t e = record(r);
+        int32_t x[10];
+        uint64_t xw[4], yw[4];
+        static_for<0, 2>([&](auto Q) {
+            ws.load<F>(Q == 0 ? ws.X : ws.Y, e, x);
+            F::mul(x, zinv, x);
+            F::to_words(x, Q == 0 ? xw : yw);
+        });
+        const uint64_t keep = lane_mask(!zero);
         static_for<0, 4>([&](auto K) {
             xw[K] &= keep;
             yw[K] = (yw[K] & keep) | (K == 0 ? (1u & ~keep) : 0u);
         });
-        store_affine_be<P>(xb, yb, sign, first + e, xw, yw);
+        sink(e, xw, yw);
     }
+};
+template <class F, class SINK>
+MA_DEV void wn_export_lane(const WnExpWs& ws, size_t L, int rounds, size_t j, const SINK& sink) {
+    shared_inv_walk<F>(rounds, WnExportItems<F, SINK>{ws, L, j, sink});
+}
+
+// lane j of L; the records leave big-endian, as records first .. of the caller's arrays
+template <class F, class P, int TAG>
+__global__ __launch_bounds__(64) void k_wn_export(WnExpWs ws, size_t L, int rounds, unsigned char* xb, unsigned char* yb, int* sign, size_t first) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < L) wn_export_lane<F>(ws, L, rounds, j, [&](size_t e, const uint64_t* xw, const uint64_t* yw) { store_affine_be<P>(xb, yb, sign, first + e, xw, yw); });
 }
 
 template <class F, class P, int TAG>

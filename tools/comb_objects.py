@@ -10,7 +10,7 @@ modarith_amd/build/ (capi_X25519, capi_ED25519_part2); one with a slash is relat
 generated ladder).  --pair compares the units its two files hold.
 
 Per kernel: the resource figures of tools/kernel_resources.py, the instruction count, a hash of the instruction text as
-tools/chain_objects.py takes it, and the loop-weighted instruction and multiply-add counts of tools/isa_mix.py; per tree `nm -D` of the
+tools/chain_objects.py takes it (and one that leaves out the pc-relative distances to the object's constant tables), and the loop-weighted instruction and multiply-add counts of tools/isa_mix.py; per tree `nm -D` of the
 library.  No GPU needed.
 """
 import argparse
@@ -26,6 +26,17 @@ import isa_mix
 import kernel_resources
 
 CURVES = ("ED25519", "ED448", "NIST256", "SECP256K1")
+
+
+def less_pc_relative(ins):
+    """the instruction text with the literal blanked in `s_getpc_b64 s[N:N+1]; s_add_u32 sN, sN, 0x...` -- that pair and no other add: the
+    distance from the program counter to a constant table of the same object, which moves when ANOTHER kernel of the object changes size"""
+    out = list(ins)
+    for k in range(1, len(out)):
+        m = re.match(r"s_getpc_b64 s\[(\d+):\d+\]$", ins[k - 1])
+        if m:
+            out[k] = re.sub(r"^(s_add_u32 s%s, s%s, )0x[0-9a-f]+$" % (m.group(1), m.group(1)), r"\1", ins[k])
+    return out
 UNITS = ["capi_%s%s" % (c, s) for s in ("G", "F", "F2") for c in CURVES]
 
 
@@ -56,7 +67,8 @@ def figures(tree, units=UNITS):
             a = isa_mix.analyse(c, latch_trips(c))
             ks[k["name"]] = dict({x: k[x] for x in kernel_resources.KEYS}, instructions=sum(a["static"].values()),
                                  weighted_valu=a["valu"], weighted_multiply_adds=a["multiplier"],
-                                 isa_sha256=hashlib.sha256("\n".join(ins for _, ins in c).encode()).hexdigest())
+                                 isa_sha256=hashlib.sha256("\n".join(ins for _, ins in c).encode()).hexdigest(),
+                                 isa_sha256_less_pc_relative=hashlib.sha256("\n".join(less_pc_relative([ins for _, ins in c])).encode()).hexdigest())
         out[u] = ks
     nm = subprocess.run(["nm", "-D", os.path.join(tree, "modarith_amd", "libmodarith_amd.so")], capture_output=True, text=True, check=True).stdout.split("\n")
     out["nm_D"] = sorted(" ".join(l.split()[-2:]) for l in nm if l.strip() and "__hip_cuid_" not in l)
@@ -76,8 +88,10 @@ def pair(parent, new):
                 units[u][nm] = dict(kp[nm], same_as_parent=True)
             else:
                 units[u][nm] = {"same_as_parent": False, "parent": kp[nm], "new": kn[nm]}
-                differs.append({"unit": u, "kernel": nm, "parent_to_new": {x: [kp[nm][x], kn[nm][x]] for x in kp[nm] if x != "isa_sha256" and kp[nm][x] != kn[nm][x]},
-                                "no_figure_higher": all(kn[nm][x] <= kp[nm][x] for x in kp[nm] if x != "isa_sha256")})
+                fig = [x for x in kp[nm] if not x.startswith("isa_sha256")]
+                differs.append({"unit": u, "kernel": nm, "parent_to_new": {x: [kp[nm][x], kn[nm][x]] for x in fig if kp[nm][x] != kn[nm][x]},
+                                "no_figure_higher": all(kn[nm][x] <= kp[nm][x] for x in fig),
+                                "same_but_for_pc_relative_literals": kp[nm]["isa_sha256_less_pc_relative"] == kn[nm]["isa_sha256_less_pc_relative"]})
     return {"units": units, "kernels": sum(len(v) for v in units.values()), "kernels_whose_instruction_text_differs": differs,
             "units_without_any_difference": [u for u in names if all(k["same_as_parent"] for k in units[u].values())],
             "nm_D_equal_but_for_hip_cuid": parent["nm_D"] == new["nm_D"], "nm_D_symbols": len(new["nm_D"])}
